@@ -26,6 +26,14 @@ value = N * K * units / max-over-ranks time.  `ranks_seen` = dist.get_world_size
 `roofline.traffic` is filled from the newest profiles/rNN_pmc_hbm.json that was measured on the kernel sources being timed
 (sha recorded by tools/pmc_hbm.sh), else null.  `cpu_baseline`: oracle/torch_cpu.py (a multi-threaded torch-CPU restatement
 doing the reference's executed work) on a bounded sample of the same workload, best of 3.
+
+A plain run does what the headline needs and nothing else: set-up, settle + --warmup steps, EXACTLY --steps timed steps, the
+line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the timing fields).  --full adds everything else the
+line can carry -- the roofline / sparsity of the render configs (HIP events around the dominant kernel inside the timed region),
+the drop-in call path (`api_*`), the dense frame, the frame without the rays-of-constants shortcut, the occupancy sweep, the
+CPU baselines with `parity` (exit code 3 on a miss) and the collectives' events of config 4; --no-cpu-baseline, --no-dense,
+--no-api and --no-sweep leave parts of it out.  --dump-outputs DIR writes what the timed path returned in its last step as
+DIR/<name>.npy (dump_outputs); the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import hashlib
@@ -275,7 +283,7 @@ def cpu_baseline_render(extra, box_bounds, frame=None, stages=None, budget_s=6.0
 
 
 # ---------------------------------------------------------------------------------------------- timing harness
-N_BLOCKS = 5               # timed blocks of --steps steps each; ms_per_step = their MEDIAN
+N_BLOCKS = 5               # the --steps timed steps run in up to N_BLOCKS blocks; ms_per_step = the MEDIAN of their per-step times
 RANK_TIMES = []            # per block (settle blocks included): the seconds every rank measured for it
 SETTLE_MIN_S, SETTLE_MAX_S, SETTLE_TOL = 0.5, 8.0, 0.02
 
@@ -322,8 +330,9 @@ def timed(fn, steps, warmup, dist, device, cpu_dist, settle_block=10, on_timed_s
          SETTLE_TOL (give up after SETTLE_MAX_S and say so); block times are max-over-ranks, so every rank takes the same
          decisions and runs the same number of steps (the training step contains collectives);
       2. the CLI's `warmup` untimed steps;
-      3. N_BLOCKS timed blocks of EXACTLY `steps` steps, each bracketed by barrier + synchronize, each the MAX over the ranks.
-    -> (median block seconds, last output, info for the JSON line)"""
+      3. EXACTLY `steps` timed steps, in min(N_BLOCKS, steps) blocks of as equal sizes as they divide into, each bracketed by
+         barrier + synchronize, each the MAX over the ranks.
+    -> (median over the blocks of seconds per step, last output, info for the JSON line)"""
     spent, steady, prev, settled, n_settle = 0.0, 0.0, None, False, 0
     settle_ms = []
     while spent < SETTLE_MAX_S:
@@ -343,24 +352,50 @@ def timed(fn, steps, warmup, dist, device, cpu_dist, settle_block=10, on_timed_s
         fn()
     if on_timed_start is not None:
         on_timed_start()
-    blocks, out = [], None
-    for _ in range(N_BLOCKS):
-        dt, out = _block(fn, steps, dist, device, cpu_dist, before=before_block)
-        blocks.append(dt)
+    n_blocks = min(N_BLOCKS, steps)
+    sizes = [steps // n_blocks + (i < steps % n_blocks) for i in range(n_blocks)]
+    blocks, out = [], None                  # seconds per step of every block
+    for size in sizes:
+        dt, out = _block(fn, size, dist, device, cpu_dist, before=before_block)
+        blocks.append(dt / size)
         if after_block is not None:
             after_block(out)
     med = float(np.median(blocks))
     per_rank = {}
-    if dist is not None and len(RANK_TIMES) >= N_BLOCKS:      # the timed blocks are the last N_BLOCKS entries
-        last = np.array(RANK_TIMES[-N_BLOCKS:])               # [block, rank]
-        per_rank = dict(ms_per_step_ranks=[float(x) for x in 1e3 * np.median(last, 0) / steps],
+    if dist is not None and len(RANK_TIMES) >= n_blocks:      # the timed blocks are the last n_blocks entries
+        last = np.array(RANK_TIMES[-n_blocks:]) / np.array(sizes, dtype=np.float64)[:, None]     # [block, rank] seconds per step
+        per_rank = dict(ms_per_step_ranks=[float(x) for x in 1e3 * np.median(last, 0)],
                         slowest_rank_per_block=[int(i) for i in last.argmax(1)])
-    info = dict(block_ms=[1e3 * b / steps for b in blocks], spread=(max(blocks) - min(blocks)) / med, settle_ms=settle_ms, **per_rank,
-                timing=f"median of {N_BLOCKS} blocks of --steps steps (each: barrier + synchronize on both sides, max over ranks) after "
-                       f"a settle phase of {n_settle} x {settle_block} steps = {spent:.2f} s "
-                       f"({'two consecutive blocks within 2 %' if settled else 'NOT settled within %.0f s' % SETTLE_MAX_S}) and "
-                       f"--warmup untimed steps")
+    info = dict(block_ms=[1e3 * b for b in blocks], block_steps=sizes, spread=(max(blocks) - min(blocks)) / med, settle_ms=settle_ms,
+                **per_rank,
+                timing=f"median per-step time of {n_blocks} blocks that share the {steps} timed steps (--steps; each block: barrier + "
+                       f"synchronize on both sides, max over ranks) after a settle phase of {n_settle} x {settle_block} steps = "
+                       f"{spent:.2f} s ({'two consecutive blocks within 2 %' if settled else 'NOT settled within %.0f s' % SETTLE_MAX_S}) "
+                       f"and --warmup untimed steps")
     return med, out, info
+
+
+DUMP_BYTES, DUMP_ARRAY_BYTES = 64 << 20, 8 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: `arrays` (name -> tensor or number: what the timed path returned in its last step) as path/<name>.npy,
+    float32 -- float64 where the output is float64 or not floating point.  An array of more than DUMP_ARRAY_BYTES keeps a fixed
+    sample of its rows: the first rows of a seed-0 permutation, in index order (the same rows for every array of that length)."""
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, x in arrays.items():
+        t = torch.as_tensor(x).detach()
+        wide = t.dtype == torch.float64 or not t.is_floating_point()
+        row_bytes = (8 if wide else 4) * (t[0].numel() if t.dim() > 0 and t.shape[0] > 0 else 1)
+        if t.dim() > 0 and t.shape[0] * row_bytes > DUMP_ARRAY_BYTES:
+            rows = np.sort(np.random.default_rng(0).permutation(t.shape[0])[:DUMP_ARRAY_BYTES // row_bytes])
+            t = t[torch.as_tensor(rows, device=t.device)]
+        a = t.cpu().numpy().astype(np.float64 if wide else np.float32)
+        total += a.nbytes
+        if total > DUMP_BYTES:
+            raise SystemExit(f"--dump-outputs: more than {DUMP_BYTES >> 20} MB at {name}")
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def ops_mod():
@@ -376,24 +411,41 @@ def bench_render(args, rank, world, device, dist):
     def start_profile():                    # HIP events around K3 from the first timed block on (settle / warm-up frames carry none)
         # The first block that records them pays for the runtime's pool of profiling signals (4 timing events per frame: the first
         # timed block read 5.1 - 7.6 ms per frame against 4.7 for the other four, on every lease; recording events alone, or two
-        # instrumented frames, did not cure it: tools/diag/first_block.py).  One block's worth of instrumented frames runs -- and
-        # is waited for, its events dropped -- in front of the timed region: the measurement's own instrumentation is not frame work.
+        # instrumented frames, did not cure it: tools/diag/first_block.py).  --steps instrumented frames run -- and are waited
+        # for, their events dropped -- in front of the timed region: the measurement's own instrumentation is not frame work.
+        # --full only: a plain run records no events.
         eng.profile = {}
         for _ in range(args.steps):
             render(eng, inp)
         torch.cuda.synchronize()
         eng.profile = {}
     elapsed, out, tinfo = timed(lambda: render(eng, inp), args.steps, args.warmup, dist, device, args.debug_single_device,
-                                on_timed_start=start_profile)
+                                on_timed_start=start_profile if args.full else None)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {k: v for k, v in out.items() if torch.is_tensor(v)})
     samples_per_frame = H * W * (N_SAMPLES + N_IMPORTANCE)
-    value = world * args.steps * samples_per_frame / elapsed
+    value = world * samples_per_frame / elapsed
+    mac = MAC_PER_ROW[args.mlp]
+    names = {1: "H36M danbo_base network", 2: "H36M danbo_fast (BASELINE config 2)", 3: "H36M danbo_base (BASELINE config 3)"}
+    result = {
+        "metric": f"ray-samples/sec at 512x512x{N_SAMPLES + N_IMPORTANCE} samples", "value": value, "unit": "ray-samples/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32" if args.mlp == "fp32" else "f32 (fp16x2-split MFMA products, fp32 accumulate)", "data": "synthetic",
+        "config": {"workload": f"{names.get(args.config, names[1])}, 512x512 rays x ({N_SAMPLES} coarse + {N_IMPORTANCE} importance) "
+                               f"samples, 1 pose / 1 camera per rank, {'per-bone box' if args.box_near_far else 'cylinder'} near/far, "
+                               "exact in-volume culling",
+                   "rays": H * W, "samples_per_ray": N_SAMPLES + N_IMPORTANCE, "parallelism": f"rays-dp{world}"},
+        **tinfo,
+    }
+    if not args.full:
+        return result
 
     # ---- roofline of the dominant kernel from the HIP events recorded inside the timed region
     prof = eng.profile["k_pe_mlp"]
     eng.profile = None
     ms = sum(e0.elapsed_time(e1) for e0, e1, _ in prof)
     rows = sum(int(c.item()) if torch.is_tensor(c) else int(c) for _, _, c in prof)
-    mac = MAC_PER_ROW[args.mlp]
     achieved = 2.0 * mac * rows / (ms * 1e-3)                # EXECUTED multiply-adds of in-volume rows only
     if args.mlp == "f16split":
         kernel, peak, peak_note = {16: "k_pe_mlp16", 32: "k_pe_mlp32"}[eng.mlp_form], PEAK_FP16_MFMA / 3.0, SPLIT_NOTE
@@ -425,19 +477,7 @@ def bench_render(args, rank, world, device, dist):
                     peak_note=peak_note,
                     note="executed flops of rows inside >=1 bone volume only; algorithmic bytes per launch = 84 B per row + 512 B of "
                          "per-ray view constants for every ray with >= 1 row; " + traffic_note)
-    names = {1: "H36M danbo_base network", 2: "H36M danbo_fast (BASELINE config 2)", 3: "H36M danbo_base (BASELINE config 3)"}
-    result = {
-        "metric": f"ray-samples/sec at 512x512x{N_SAMPLES + N_IMPORTANCE} samples", "value": value, "unit": "ray-samples/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32" if args.mlp == "fp32" else "f32 (fp16x2-split MFMA products, fp32 accumulate)", "data": "synthetic",
-        "config": {"workload": f"{names.get(args.config, names[1])}, 512x512 rays x ({N_SAMPLES} coarse + {N_IMPORTANCE} importance) "
-                               f"samples, 1 pose / 1 camera per rank, {'per-bone box' if args.box_near_far else 'cylinder'} near/far, "
-                               "exact in-volume culling",
-                   "rays": H * W, "samples_per_ray": N_SAMPLES + N_IMPORTANCE, "parallelism": f"rays-dp{world}"},
-        "in_volume_fraction": rows / (N_BLOCKS * args.steps * samples_per_frame), "sparsity": sparsity,
-        "roofline": roofline, **tinfo,
-    }
+    result.update(in_volume_fraction=rows / (args.steps * samples_per_frame), sparsity=sparsity, roofline=roofline)
     if rank == 0 and world == 1 and not args.no_api:
         result.update(bench_through_caster(args, device, extra, inp, out))
     if rank == 0 and world == 1:
@@ -484,8 +524,7 @@ def bench_render(args, rank, world, device, dist):
 
                 def start2(e=e2):
                     e.profile = {}
-                dt, _, ti = timed(lambda: render(e2, i2), 10, 0, None, device, False, on_timed_start=start2)
-                dt /= 10
+                dt, _, ti = timed(lambda: render(e2, i2), 10 * N_BLOCKS, 0, None, device, False, on_timed_start=start2)
                 r2 = sum(int(c.item()) for _, _, c in e2.profile["k_pe_mlp"]) / (10 * N_BLOCKS)
                 sweep.append(dict(camera_distance=dist_, in_volume_fraction=r2 / samples_per_frame, value=samples_per_frame / dt,
                                   ms_per_step=1e3 * dt, spread=ti["spread"]))
@@ -503,8 +542,8 @@ def bench_through_caster(args, device, extra, inp, engine_out):
     """The same frame through the DROP-IN call path (missing 1): `core.trainer.render(H, W, focal, chunk=4096,
     rays=..., kp_batch=..., skts=..., **render_kwargs_test)` exactly as run_render.py / render_path call it (reference
     run_nerf.py:64-91 -> core/trainer.py:96-161 -> batchify_rays -> ray_caster(...)), on a caster built by create_raycaster from the
-    shipped config file and loaded with the same weights.  -> api_ms_per_step / api_value (median of N_BLOCKS blocks of --steps
-    frames, same bracketing as the headline) and whether its maps are bit-identical to the engine-level frame that was timed."""
+    shipped config file and loaded with the same weights.  -> api_ms_per_step / api_value (--steps timed frames, same blocks and
+    bracketing as the headline) and whether its maps are bit-identical to the engine-level frame that was timed."""
     from core import trainer
     from core.config import parse_args
     from core.raycasters import create_raycaster
@@ -531,7 +570,7 @@ def bench_through_caster(args, device, extra, inp, engine_out):
     elapsed, out, tinfo = timed(frame, args.steps, args.warmup, None, device, False)
     same = all(torch.equal(out[k].reshape(engine_out[k].shape), engine_out[k]) for k in engine_out if torch.is_tensor(engine_out[k]) and k in out)
     del caster
-    return dict(api_ms_per_step=1e3 * elapsed / args.steps, api_value=args.steps * n * (N_SAMPLES + N_IMPORTANCE) / elapsed,
+    return dict(api_ms_per_step=1e3 * elapsed, api_value=n * (N_SAMPLES + N_IMPORTANCE) / elapsed,
                 api_spread=tinfo["spread"], api_equals_engine=bool(same),
                 api_note="the same frame through core.trainer.render(H, W, focal, chunk=4096, rays=..., **render_kwargs_test) on a caster "
                          "from create_raycaster(configs/h36m_zju/" + cfg_file + "): the call run_render.py makes per image; the caster "
@@ -595,7 +634,8 @@ def bench_train(args, rank, world, device, dist):
     # The workload must not depend on how long a box takes to settle (every step is a real Adam update, the bone volumes
     # the model learns change the row count, and the settle phase runs a box-dependent number of steps): one step builds the engine,
     # its state is snapshotted, and the snapshot is restored in front of the warm-up steps and of EVERY timed block -- each block
-    # trains steps 1 .. K from the same weights, moments and random stream.  rows_per_block: what the last step of each block saw.
+    # trains steps 1 .. k (its `block_steps`) from the same weights, moments and random stream.  rows_per_block: what the last step
+    # of each block saw.
     one()
     torch.cuda.synchronize()
     eng = trainer.engine
@@ -610,12 +650,14 @@ def bench_train(args, rank, world, device, dist):
         rows_per_block.append(int(trainer.last_preds["counts"][4].item()))
     coll = []
 
-    def start_coll():                      # HIP events around the two all-reduces of every step of the timed blocks
+    def start_coll():                      # --full: HIP events around the two all-reduces of every step of the timed blocks
         if dist is not None or args.nccl_world_1:
             trainer.collective_events = coll
     elapsed, (loss, stats), tinfo = timed(one, args.steps, args.warmup, dist, device, args.debug_single_device, settle_block=50,
-                                          before_block=restore, after_block=note_rows, on_timed_start=start_coll)
+                                          before_block=restore, after_block=note_rows, on_timed_start=start_coll if args.full else None)
     trainer.collective_events = None
+    if rank == 0 and args.dump_outputs:     # the loss terms of the last step and the parameters it left (read before any other step)
+        dump_outputs(args.dump_outputs, {**{k: loss[k] for k in loss}, "params": trainer.engine.flat_p})
     collective = None
     if coll:
         torch.cuda.synchronize()
@@ -638,7 +680,7 @@ def bench_train(args, rank, world, device, dist):
     mac_fwd = 195 * 256 + 4 * 256 * 256 + 451 * 256 + 2 * 256 * 256 + 256 + 256 * 128 + 128 * 3
     mac_dx = 3 * 128 + 128 * 256 + 256 + 6 * 256 * 256 + 256 * 451 + 256 * 195    # rgb^T, W_fv^T, alpha, trunk 7..1 (5: 451 out), layer 0
     mac_ref = 195 * 256 + 4 * 256 * 256 + 451 * 256 + 2 * 256 * 256 + 257 * 256 + 411 * 128 + 128 * 3   # the reference's forward per row
-    ms = 1e3 * elapsed / args.steps
+    ms = 1e3 * elapsed
     if dist is not None:                 # whole-job executed rows: sum over the ranks
         rt = torch.tensor([float(rows), float(in_vol)], dtype=torch.float64, device="cpu" if args.debug_single_device else device)
         dist.all_reduce(rt)
@@ -672,8 +714,8 @@ def bench_train(args, rank, world, device, dist):
         "rows_per_step": rows, "in_volume_fraction": in_vol / (R_global * S), "loss": float(loss["total_loss"]),
         "rows_per_block": rows_per_block,
         "rows_note": "every timed block (and the warm-up) starts from the SAME snapshot of weights, Adam moments and random stream, taken "
-                     "after the engine's first step: each block trains steps 2 .. K + 1 of the same run, whatever the settle phase did "
-                     "(round 4 timed a model that had trained through a box-dependent number of settle steps: 50 k .. 64 k rows)",
+                     "after the engine's first step: each block trains steps 2 .. k + 1 of the same run (k: its block_steps), whatever the "
+                     "settle phase did (round 4 timed a model that had trained through a box-dependent number of settle steps: 50 k .. 64 k rows)",
         "roofline": dict(bound="mfma", kernel="k_train_mlp_fwd x 2 + k_train_mlp_bwd + k_dw16 (whole step)", achieved=achieved / 1e12,
                          peak=peak / 1e12, unit="TFLOP/s", frac=achieved / peak, traffic=traffic, flop_per_row=2 * (2 * mac_fwd + mac_dx),
                          flop_per_row_reference=2 * (3 * mac_ref),
@@ -694,7 +736,7 @@ def bench_train(args, rank, world, device, dist):
     }
     if hbm is not None:
         result["hbm"] = hbm
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline_train(targs, caster, batch, poses)
         restore()
         result["parity"] = train_parity_block(targs, caster, trainer, batch, poses, device)
@@ -806,10 +848,12 @@ def bench_anerf(args, rank, world, device, dist):
     S, Sf = 48, 16
     run = lambda: eng.render(inp["rays_o"], inp["rays_d"], inp["skts"], inp["bones"], inp["cyls"], inp["cam_idx"], S, Sf)  # noqa: E731
     elapsed, out, tinfo = timed(run, args.steps, args.warmup, dist, device, args.debug_single_device, settle_block=2)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {k: v for k, v in out.items() if torch.is_tensor(v)})
     n = len(ro) * (S + Sf)
     Wd, inc, VW = cfg["W"], 432, cfg["view_W"]
     mac = inc * Wd + 4 * Wd * Wd + (inc + Wd) * Wd + 2 * Wd * Wd + Wd + Wd * VW + 24 * VW + 3 * VW
-    ms = 1e3 * elapsed / args.steps
+    ms = 1e3 * elapsed
     achieved = 2.0 * n * mac / (ms * 1e-3)
     peak = PEAK_FP16_MFMA / 3.0
     # HBM bytes of a frame from the PMC passes of tools/pmc_anerf.sh, quoted only for the kernel sources they were measured on
@@ -841,7 +885,7 @@ def bench_anerf(args, rank, world, device, dist):
     }
     if hbm is not None:
         result["hbm"] = hbm
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # oracle/torch_cpu.AnerfTorchCPU: the same multi-threaded torch-CPU restatement the DANBO configs are timed against (the
         # numpy oracle stays the parity checker: it is not a fair clock), thread count chosen on a probe, best of 3
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -966,9 +1010,9 @@ def bench_dry_run(args, rank, world, device, dist):
         time.sleep(mine)
     elapsed, _, tinfo = timed(one, args.steps, args.warmup, dist, "cpu", True, settle_block=5)
     units = 1000
-    return {"metric": "DRY RUN of the launch path (no GPU work, not a measurement)", "value": world * args.steps * units / elapsed,
+    return {"metric": "DRY RUN of the launch path (no GPU work, not a measurement)", "value": world * units / elapsed,
             "unit": "made-up units/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed, "higher_is_better": True,
             "scaling": args.scaling or "weak", "vs_baseline": None, "dtype": "none", "data": "none", **tinfo,
             "config": {"workload": f"dry run of --config {args.config}", "parallelism": f"rays-dp{world}", "units_per_step_and_rank": units}}
 
@@ -1001,7 +1045,14 @@ def main():
                     help="dev: launch / rendezvous / timing harness only, a host no-op as the step (gloo, no GPU needed); not a measurement")
     ap.add_argument("--mlp", choices=["f16split", "fp32"], default="f16split",
                     help="f16split: fp32-accurate products as 3 fp16 MFMAs (default); fp32: exact fp32 MFMA kernels")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: roofline, api / dense / sweep timings, CPU baseline "
+                         "and parity, collective events (the --no-* options leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32 / float64, <= 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.scaling == "strong" and args.config != 4:
         raise SystemExit("--scaling strong is defined for --config 4 (the training batch); the render configs shard views: weak")
     if args.gpus < 1:

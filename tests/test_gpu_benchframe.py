@@ -62,3 +62,34 @@ def test_oracle_on_the_bench_frame(config):
     assert p["parity_ok"] is True and p["parity_ok_timed_frame"] is True
     # the maps of the timed frame against the oracle's, after importance resampling
     assert p["max_abs_rgb"] < 1e-4 and p["max_abs_acc"] < 1e-4 and p["psnr_rgb_db"] > 90.0
+
+
+def test_plain_bench_run_dumps_the_outputs_of_its_last_timed_frame(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` without --full: EXACTLY K timed steps, the headline fields and none of
+    what --full adds; DIR holds the outputs of the last timed frame (float32, <= 64 MB, a fixed sample of the rows of the large
+    ones), bit for bit those of the same frame rendered here."""
+    import json
+    import subprocess
+    sys.path.insert(0, ROOT)
+    import bench
+    got_dir, ref_dir = tmp_path / "bench", tmp_path / "here"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--dump-outputs", str(got_dir)],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    r = json.loads(lines[0])
+    assert r["steps"] == 3 and sum(r["block_steps"]) == 3 and r["ms_per_step"] > 0 and r["higher_is_better"] is True
+    assert r["unit"] == "ray-samples/s" and abs(r["value"] - 512 * 512 * 64 / (r["ms_per_step"] * 1e-3)) <= 1e-9 * r["value"]
+    assert not {"roofline", "sparsity", "cpu_baseline", "parity", "api_value", "dense_value", "occupancy_sweep"} & set(r)
+    got = {f.stem: np.load(f) for f in got_dir.glob("*.npy")}
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20 and all(a.dtype == np.float32 for a in got.values())
+    assert got["rgb_map"].shape == (512 * 512, 3) and 0 < got["alpha"].shape[0] < 512 * 512 and got["alpha"].shape[1] == 64
+    bench.N_SAMPLES, bench.N_IMPORTANCE, box = bench.CONFIGS[1]
+    eng, inp, _ = bench.build_workload(torch.device(DEV), view=0)
+    eng.cfg["use_volume_near_far"] = box
+    out = bench.render(eng, inp)
+    bench.dump_outputs(str(ref_dir), {k: v for k, v in out.items() if torch.is_tensor(v)})
+    assert sorted(got) == sorted(f.stem for f in ref_dir.glob("*.npy"))
+    for k, a in got.items():
+        np.testing.assert_array_equal(a, np.load(ref_dir / f"{k}.npy"), err_msg=k)

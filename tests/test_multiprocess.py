@@ -211,17 +211,17 @@ def test_bench_gpus_flag_starts_the_ranks_itself():
     """`python bench.py --gpus 2 ...` from a shell with no RANK / WORLD_SIZE exported starts two ranks (launch_ranks) and prints ONE
     line with n_gpus = ranks_seen = 2.  --dry-run: a host no-op as the step, so the command path runs without a GPU."""
     r = _run_bench("--gpus", "2", "--dry-run", "--config", "4", "--scaling", "strong", "--steps", "4", "--warmup", "1")
-    assert r["n_gpus"] == 2 and r["ranks_seen"] == 2 and r["scaling"] == "strong" and r["steps"] == 4
-    r1 = _run_bench("--dry-run", "--steps", "2", "--warmup", "0")
-    assert r1["n_gpus"] == 1 and r1["ranks_seen"] == 1
+    assert r["n_gpus"] == 2 and r["ranks_seen"] == 2 and r["scaling"] == "strong" and r["steps"] == 4 and r["block_steps"] == [1] * 4
+    r1 = _run_bench("--dry-run", "--steps", "7", "--warmup", "0")
+    assert r1["n_gpus"] == 1 and r1["ranks_seen"] == 1 and r1["block_steps"] == [2, 2, 1, 1, 1]      # --steps = the timed steps
 
 
 def test_bench_value_is_units_over_the_slowest_ranks_time():
     """with UNEQUAL rank speeds (rank 0 sleeps 2 ms per step, rank 1 6 ms; gloo, world 2, no GPU) the line's
     ms_per_step is the MAX over the ranks, value = N x K x units / that time, and the line says which rank was slow:
     ms_per_step_ranks lists every rank's own time, slowest_rank_per_block names the rank behind each block's maximum."""
-    r = _run_bench("--gpus", "2", "--dry-run", "--dry-run-ms", "2,6", "--steps", "10", "--warmup", "1")
-    assert r["n_gpus"] == 2 and r["ranks_seen"] == 2 and len(r["block_ms"]) == 5
+    r = _run_bench("--gpus", "2", "--dry-run", "--dry-run-ms", "2,6", "--steps", "50", "--warmup", "1")
+    assert r["n_gpus"] == 2 and r["ranks_seen"] == 2 and len(r["block_ms"]) == 5 and r["block_steps"] == [10] * 5
     fast, slow = r["ms_per_step_ranks"]
     assert 2.0 <= fast < 4.5 and 6.0 <= slow < 8.5, r["ms_per_step_ranks"]          # each rank's OWN time (sleep + overhead)
     assert r["slowest_rank_per_block"] == [1] * 5
@@ -249,7 +249,8 @@ def test_bench_weak_scaling_on_two_ranks_of_one_gpu(config):
     config 4 weak (every rank its own 3072-ray batch, two in-place all-reduces per step) through the real launcher with two ranks that
     share cuda:0 (gloo carries the collectives): one line, ranks_seen = 2, per-rank lists present, and -- two ranks taking turns on one
     device -- a whole-job value close to what one rank alone reaches."""
-    flags = ("--config", config, "--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--no-dense", "--no-sweep", "--no-api")
+    flags = ("--config", config, "--steps", "25", "--warmup", "1", "--no-cpu-baseline", "--no-dense", "--no-sweep", "--no-api",
+             *(("--full",) if config == "4" else ()))          # --full: the collectives' events (collective_ms)
     two = _run_bench("--gpus", "2", "--debug-single-device", *flags)
     one = _run_bench("--gpus", "1", *flags)
     assert two["n_gpus"] == 2 and two["ranks_seen"] == 2 and one["n_gpus"] == 1 and two["scaling"] == "weak"

@@ -13,15 +13,15 @@ import bench
 dev = torch.device("cuda", 0)
 mode = sys.argv[1]
 if mode == "render_fn":
-    args = argparse.Namespace(steps=20, warmup=3, mlp="f16split", box_near_far=False, config=1, no_cpu_baseline=True, no_dense=True, no_sweep=True,
-                              debug_single_device=False, gpus=1)
+    args = argparse.Namespace(steps=100, warmup=3, mlp="f16split", box_near_far=False, config=1, full=True, no_cpu_baseline=True, no_dense=True,
+                              no_sweep=True, no_api=True, dump_outputs=None, debug_single_device=False, gpus=1)
     r = bench.bench_render(args, 0, 1, dev, None)
     print(mode, [round(b, 3) for b in r["block_ms"]])
 elif mode == "set_device":
     torch.cuda.set_device(0)
     eng, inp, _ = bench.build_workload(dev, view=0, mlp_mode="f16split")
     eng.cfg["use_volume_near_far"] = False
-    med, out, info = bench.timed(lambda: bench.render(eng, inp), 20, 3, None, dev, False, on_timed_start=lambda: setattr(eng, "profile", {}))
+    med, out, info = bench.timed(lambda: bench.render(eng, inp), 100, 3, None, dev, False, on_timed_start=lambda: setattr(eng, "profile", {}))
     print(mode, [round(b, 3) for b in info["block_ms"]])
 elif mode in ("prime_frame", "no_profile", "prime_sleep"):
     torch.cuda.set_device(0)
@@ -37,12 +37,12 @@ elif mode in ("prime_frame", "no_profile", "prime_sleep"):
             import time
             torch.cuda.synchronize(); time.sleep(0.2)
             eng.profile = {}
-    med, out, info = bench.timed(lambda: bench.render(eng, inp), 20, 3, None, dev, False, on_timed_start=hook)
+    med, out, info = bench.timed(lambda: bench.render(eng, inp), 100, 3, None, dev, False, on_timed_start=hook)
     print(mode, [round(b, 3) for b in info["block_ms"]])
 elif mode in ("nodev", "dev_late"):
     eng, inp, _ = bench.build_workload(dev, view=0, mlp_mode="f16split")
     if mode == "dev_late":
         torch.cuda.set_device(0)
     eng.cfg["use_volume_near_far"] = False
-    med, out, info = bench.timed(lambda: bench.render(eng, inp), 20, 3, None, dev, False, on_timed_start=lambda: setattr(eng, "profile", {}))
+    med, out, info = bench.timed(lambda: bench.render(eng, inp), 100, 3, None, dev, False, on_timed_start=lambda: setattr(eng, "profile", {}))
     print(mode, [round(b, 3) for b in info["block_ms"]])

@@ -1,12 +1,15 @@
 #!/bin/bash
 # usage: prof.sh TAG  -> runs tests (quick subset) + rocprof bench, prints per-kernel table
 TAG=$1
+R=$(cd "$(dirname "$0")/.." && pwd)
+OUT=${PROF_OUT:-$R/prof_out}          # rocprofv3's directory and the bench log
+mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/gpurun_out/prof_$TAG -o $TAG -- python3 $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-dense --no-sweep > $GRAFT_REPO_ROOT/gpurun_out/prof_${TAG}_bench.log 2>&1
-grep -o '"value": [0-9.]*\|"ms_per_step": [0-9.]*\|"achieved": [0-9.]*\|"avg_launch_ms": [0-9.]*' $GRAFT_REPO_ROOT/gpurun_out/prof_${TAG}_bench.log | tr '\n' ' '; echo
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -o $TAG -- python3 $R/bench.py --full --steps 25 --warmup 1 --no-cpu-baseline --no-dense --no-sweep > $OUT/prof_${TAG}_bench.log 2>&1
+grep -o '"value": [0-9.]*\|"ms_per_step": [0-9.]*\|"achieved": [0-9.]*\|"avg_launch_ms": [0-9.]*' $OUT/prof_${TAG}_bench.log | tr '\n' ' '; echo
 python3 - <<PY
 import csv,os
-rows=list(csv.DictReader(open(os.environ["GRAFT_REPO_ROOT"]+"/gpurun_out/prof_$TAG/${TAG}_kernel_stats.csv")))
+rows=list(csv.DictReader(open("$OUT/prof_$TAG/${TAG}_kernel_stats.csv")))
 # frames of the run (settle phase + warm-up + timed blocks + the reference frame): the final composite runs once per frame
 frames = max([int(r["Calls"]) for r in rows if "k_composite_merged" in r["Name"]] + [1])
 for r in rows[:10]:
