@@ -47,8 +47,10 @@ SIGNATURES = {
     "danbo_composite_bwd": [P, P, P, I, I, F, P, P, P, P, P],
     "danbo_bone_gather_bwd": [P, P, P, P, I, I, I, P, P, P, P, P, I, P, P, P, P],
     "danbo_importance_samples": [P, P, I, I, I, P, P, P, P, P],
+    "danbo_importance_samples_pdf": [P, P, I, I, I, P, I, P, P, P, P, P, P],
     "danbo_merge_samples": [P, P, P, I, I, I, I, P, P],
     "danbo_composite_importance_fwd": [P, P, P, P, P, I, I, I, F, P, P, P, P, P, P, P, P, P, P, P, P, P],
+    "danbo_composite_importance_pdf_fwd": [P, P, P, P, P, I, I, I, F, P, P, I, P, P, P, P, P, P, P, P, P, P, P],
     "danbo_composite_merged_fwd": [P, P, P, P, P, P, P, P, I, I, I, F, P, P, P, P, P, P, P, P, P, P],
     "danbo_flat_rays": [P, P, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, P],
     "danbo_anerf_encode_fwd": [P, P, P, P, I, I, I, P, P, P, F, I, c_long, I, P, P, P],

@@ -343,13 +343,20 @@ def composite(raw, z, rays_d, B=1.0, noise=None, bits=None, raw_empty=None, flat
     return dict(rgb_map=rgb, disp_map=disp, acc_map=acc, weights=w, alpha=al)
 
 
-def importance_samples(z, weights, Sf, u=None, flat=None):
+def importance_samples(z, weights, Sf, u=None, flat=None, two_net=False):
     """flat: flat_rays()'s result (64 < S <= 256, Sf <= 64) -- only its listed rays are resampled, into its z_fine (the rows of
-    the other rays are there; their z_sorted / sorted_idx rows are never made)"""
+    the other rays are there; their z_sorted / sorted_idx rows are never made).
+    two_net: the pdf of a caster with a separate fine network (isample_from_lineseg(is_only=False), danbo_importance_samples_pdf)"""
     R, S = z.shape
     dev = z.device
     zs = torch.empty(R, S + Sf, device=dev, dtype=torch.float32)
     idx = torch.empty(R, S + Sf, device=dev, dtype=torch.int32)
+    if two_net:
+        zf = flat["z_fine"] if flat is not None else torch.empty(R, Sf, device=dev, dtype=torch.float32)
+        assert zf.shape == (R, Sf)
+        _call("danbo_importance_samples_pdf", _p(_f32(z, "z")), _p(_f32(weights, "weights")), R, S, Sf, _p(_f32(u, "u")), 1,
+              _p(zf), _p(zs), _p(idx), _p(flat["ray_list"] if flat else None), _p(flat["ray_count"] if flat else None), _stream())
+        return zs, zf, idx
     if flat is not None:
         zf = flat["z_fine"]
         assert zf.shape == (R, Sf)
@@ -392,11 +399,12 @@ def flat_rays(t_lo, ray_flat, S, Sf, want_weights=False, rows_later=False, cnt=N
 
 
 def composite_importance(raw, z, rays_d, Sf, B=1.0, noise=None, u=None, bits=None, raw_empty=None, want_weights=True,
-                         flat=None):
+                         flat=None, two_net=False):
     """coarse composite + importance resampling in one launch (S, Sf <= 64) ->
     (out0 dict, z_sorted, z_fine, sorted_idx); bits/raw_empty: un-filled raw (see danbo_hip.h).
     flat: flat_rays()'s result -- only its listed rays are composited, into its buffers (the rows of the other rays are already
-    there; their z_sorted / sorted_idx rows are never made)."""
+    there; their z_sorted / sorted_idx rows are never made).
+    two_net: resample with the two-network pdf (danbo_composite_importance_pdf_fwd)."""
     raw, z, rays_d = _f32(raw, "raw"), _f32(z, "z"), _f32(rays_d, "rays_d")
     R, S = z.shape
     dev = raw.device
@@ -413,9 +421,10 @@ def composite_importance(raw, z, rays_d, Sf, B=1.0, noise=None, u=None, bits=Non
         zf = torch.empty(R, Sf, device=dev, dtype=torch.float32)
     zs = torch.empty(R, S + Sf, device=dev, dtype=torch.float32)
     idx = torch.empty(R, S + Sf, device=dev, dtype=torch.int32)
-    _call("danbo_composite_importance_fwd", _p(raw), _p(_f32(raw_empty, "raw_empty")), _p(bits), _p(z), _p(rays_d), R, S,
-          int(Sf), float(B), _p(_f32(noise, "noise")), _p(_f32(u, "u")), _p(rgb), _p(disp), _p(acc), _p(w), _p(al), _p(zf),
-          _p(zs), _p(idx), _p(flat["ray_list"] if flat else None), _p(flat["ray_count"] if flat else None), _stream())
+    # (pdf 0 runs exactly the kernels of danbo_composite_importance_fwd)
+    _call("danbo_composite_importance_pdf_fwd", _p(raw), _p(_f32(raw_empty, "raw_empty")), _p(bits), _p(z), _p(rays_d), R, S,
+          int(Sf), float(B), _p(_f32(noise, "noise")), _p(_f32(u, "u")), int(bool(two_net)), _p(rgb), _p(disp), _p(acc), _p(w), _p(al),
+          _p(zf), _p(zs), _p(idx), _p(flat["ray_list"] if flat else None), _p(flat["ray_count"] if flat else None), _stream())
     return dict(rgb_map=rgb, disp_map=disp, acc_map=acc, weights=w, alpha=al), zs, zf, idx
 
 

@@ -36,7 +36,9 @@ def get_grad_vars(args, ray_caster):
             p.requires_grad = 'framecodes' in n
     out = [p for p in net.parameters() if p.requires_grad]
     if net_fine is not None and not args.single_net:
-        out += [p for p in net_fine.parameters() if p.requires_grad]
+        # (A-NeRF's cutoff embedders are one module shared by both networks, as in the reference: listed once)
+        seen = {id(p) for p in out}
+        out += [p for p in net_fine.parameters() if p.requires_grad and id(p) not in seen]
     return out
 
 
@@ -131,8 +133,6 @@ class RayCaster(nn.Module):
         self.network, self.network_fine = network, network_fine
         self.rest_poses, self.skel_type, self.align_bones = rest_poses, skel_type or SMPLSkeleton, align_bones
         self.single_net = single_net
-        if not single_net and network_fine is not None:
-            raise NotImplementedError("single_net=False (separate fine network) is out of scope")
         if align_bones is not None:
             self.init_bone_align_transforms()
 
@@ -157,8 +157,15 @@ class RayCaster(nn.Module):
     def get_networks(self):
         return self.network, self.network_fine
 
+    @property
+    def two_net(self):
+        """a separate fine network (single_net = False): it renders all S + Sf samples of the second pass"""
+        return self.network_fine is not None and self.network_fine is not self.network
+
     def update_embed_fns(self, global_step, args):
         self.network.update_embed_fns(global_step, args)
+        if self.two_net:      # reference :593-597: A-NeRF's cutoff tau follows the schedule in both networks
+            self.network_fine.update_embed_fns(global_step, args)
 
     # ---- checkpoint format of the reference (:601-637): one sub-dict per sub-module ----
     @staticmethod
@@ -199,15 +206,31 @@ class RayCaster(nn.Module):
         with torch.no_grad():
             return self.render_rays(*args, **kwargs)
 
-    def _engine(self, refresh=True):
-        dev = next(self.network.parameters()).device
+    def _engine(self, refresh=True, network=None):
+        network = self.network if network is None else network
+        dev = next(network.parameters()).device
         if self.transforms.device != dev:
             self.transforms = self.transforms.to(dev)
-        eng = self.network.engine(self.transforms[0])
+        eng = network.engine(self.transforms[0])
         eng.cfg['use_volume_near_far'] = bool(getattr(self, 'use_volume_near_far', False))
         if refresh:      # re-packs the kernels' weight buffers when a parameter version changed: the eval path needs that
             eng.refresh()
         return eng
+
+    def _engines(self, preproc_kwargs):
+        """-> (coarse engine, fine engine or None), both at the caller's density scale"""
+        eng = self._engine()
+        eng.cfg['density_scale'] = preproc_kwargs.get('density_scale', eng.cfg['density_scale'])
+        fine = self._engine(network=self.network_fine) if self.two_net else None
+        if fine is not None:
+            fine.cfg['density_scale'] = eng.cfg['density_scale']
+        return eng, fine
+
+    @staticmethod
+    def _render(eng, fine, *args, **kwargs):
+        if fine is None:
+            return eng.render(*args, **kwargs)
+        return eng.render_two_net(fine, *args, **kwargs)
 
     @staticmethod
     def _per_pose(x, G):
@@ -226,10 +249,9 @@ class RayCaster(nn.Module):
         # the two flags (raycasters.py:265-266) but never hands them to raw2outputs (:334-337, :373-375), whose colourings
         # (nerf.py:306-311) would moreover need raw[..., 4:], which no shipped network produces.  The colourings themselves are
         # available on NeRF.raw2outputs (core/networks/nerf.py) for a caller that passes the assignment logits in raw[..., 4:].
-        eng = self._engine()
+        eng, fine = self._engines(preproc_kwargs)
         G = int(N_uniques)
         skts_g, bones_g, cyls_g = self._per_pose(skts, G), self._per_pose(bones, G), self._per_pose(cyls, G)
-        eng.cfg['density_scale'] = preproc_kwargs.get('density_scale', eng.cfg['density_scale'])
         R = ray_batch.shape[0]
 
         def chain(rb, skts_g, bones_g, cyls_g, cams):
@@ -237,14 +259,15 @@ class RayCaster(nn.Module):
             near, far = ops.near_far_cylinder(rays_o, rays_d, cyls_g, 0., 1., R, rb[:, 6], rb[:, 7])
             if eng.cfg['use_volume_near_far']:
                 ops.near_far_boxes(rays_o, rays_d, skts_g, eng.align, eng.axis_scale, near, far)
-            return eng.render(rays_o, rays_d, skts_g, bones_g, cyls_g, cams, N_samples, N_importance, near_far=(near, far))
+            return self._render(eng, fine, rays_o, rays_d, skts_g, bones_g, cyls_g, cams, N_samples, N_importance,
+                                near_far=(near, far))
 
         # Small ray chunks (the reference casts `chunk // 8` = 512 rays at a time during validation) are launch-bound: the
         # ~25 kernels of the chain are captured once per chunk shape as a HIP graph and replayed.
         if self.use_graphs and R <= self.graph_max_rays and isinstance(eng, DanboEngine):
             key = (R, G, int(N_samples), int(N_importance), cams is not None, eng.cfg['use_volume_near_far'],
                    float(eng.cfg['density_scale']))
-            return self._graphs.run(eng, key, chain, ray_batch, skts_g, bones_g, cyls_g, cams)
+            return self._graphs.run([eng] if fine is None else [eng, fine], key, chain, ray_batch, skts_g, bones_g, cyls_g, cams)
         return chain(ray_batch, skts_g, bones_g, cyls_g, cams)
 
     @staticmethod
@@ -263,10 +286,9 @@ class RayCaster(nn.Module):
         if (self.training or fwd_type or N_importance <= 0 or perturb or raw_noise_std or ray_noise_std or lindisp
                 or int(N_uniques) != 1 or not all(self._one_pose(x) for x in (skts, bones, cyls))):
             return None
-        eng = self._engine()
+        eng, fine = self._engines(preproc_kwargs)
         if not isinstance(eng, DanboEngine) or N_samples > 256 or N_importance > 64:
             return None
-        eng.cfg['density_scale'] = preproc_kwargs.get('density_scale', eng.cfg['density_scale'])
         skts_g, bones_g, cyls_g = skts[:1].contiguous(), bones[:1].contiguous(), cyls[:1].contiguous()
         chunk = int(chunk)
         R = rays[0].shape[0] if rays is not None else ray_batch.shape[0]
@@ -285,8 +307,8 @@ class RayCaster(nn.Module):
                 near, far = ops.near_far_cylinder(rays_o, rays_d, cyls_g, 0., 1., chunk, rb[:, 6], rb[:, 7])
             if eng.cfg['use_volume_near_far']:
                 ops.near_far_boxes(rays_o, rays_d, skts_g, eng.align, eng.axis_scale, near, far)
-            return eng.render(rays_o, rays_d, skts_g, bones_g, cyls_g, None if cams is None else cams[a:b], N_samples, N_importance,
-                              near_far=(near, far))
+            return self._render(eng, fine, rays_o, rays_d, skts_g, bones_g, cyls_g, None if cams is None else cams[a:b], N_samples,
+                                N_importance, near_far=(near, far))
 
         if R <= sub:
             return cast(0, R)
@@ -297,7 +319,9 @@ class RayCaster(nn.Module):
                           subject_idxs=None, lindisp=False, perturb=0., N_importance=0, raw_noise_std=0.,
                           ray_noise_std=0., N_uniques=1, preproc_kwargs={}, netchunk=1024 * 64, **kwargs):
         """Differentiable two-pass render (reference render_rays :245-377 in training mode): sampling is
-        detached, the network and the compositing carry gradients (core/train_path.py)."""
+        detached, the network and the compositing carry gradients (core/train_path.py).  With a separate fine network
+        (single_net = False) the fine network runs on all S + Sf sorted samples and its raw is composited as it is; the
+        assignment logits of the DANBO loss are then the fine pass's (reference :350-375)."""
         if N_importance <= 0 or lindisp or ray_noise_std:
             raise NotImplementedError("training needs N_importance > 0, lindisp=False, ray_noise_std=0")
         # the training forward reads the parameters themselves: no re-pack of the eval kernels' buffers after every optimizer step
@@ -316,20 +340,37 @@ class RayCaster(nn.Module):
             z = ops.coarse_samples(near, far, N_samples, t_rand)
         align = self.transforms[:1, None].to(rays_o.device)
 
-        shared = {}   # per-pose volumes, per-ray view inputs and the empty-space evaluation are the same in both passes
+        # per-pose volumes, per-ray view inputs and the empty-space evaluation are the same in both passes of ONE network: one
+        # dict per network (a separate fine network has volumes and view constants of its own)
+        shared = {id(self.network): {}}
 
-        def net(zv):
+        def net(zv, network):
             pts = rays_o[:, None, :] + rays_d[:, None, :] * zv[:, :, None]
             inputs = dict(pts=pts, kps=None, skts=skts_g, bones=bones_g, align_transforms=align, N_uniques=G,
-                          rays_o=rays_o[:, None], rays_d=rays_d[:, None], cam_idxs=cams, shared=shared)
-            return self.network(inputs)
+                          rays_o=rays_o[:, None], rays_d=rays_d[:, None], cam_idxs=cams,
+                          shared=shared.setdefault(id(network), {}))
+            return network(inputs)
 
-        raw, enc = net(z)
+        raw, enc = net(z, self.network)
         out0 = self.network.raw2outputs(raw, z, rays_d, raw_noise_std=raw_noise_std, B=B)
         with torch.no_grad():
             u = torch.rand(R, N_importance, device=rays_o.device) if perturb > 0. else None
-            z_all, z_fine, order = ops.importance_samples(z, out0['weights'], N_importance, u)
-        raw_f, enc_f = net(z_fine)
+            if self.two_net:
+                z_all, z_fine, order = ops.importance_samples(z, out0['weights'], N_importance, u, two_net=True)
+            else:
+                z_all, z_fine, order = ops.importance_samples(z, out0['weights'], N_importance, u)
+        if self.two_net:
+            raw_f, enc_f = net(z_all, self.network_fine)
+            out = self.network_fine.raw2outputs(raw_f, z_all, rays_d, raw_noise_std=raw_noise_std, B=B)
+            ret = dict(rgb_map=out['rgb_map'], disp_map=out['disp_map'], acc_map=out['acc_map'], alpha=out['alpha'],
+                       T_i=out['weights'], rgb0=out0['rgb_map'], disp0=out0['disp_map'], acc0=out0['acc_map'],
+                       alpha0=out0['alpha'])
+            if 'confd' in enc_f:
+                ret.update(confd=enc_f['confd'], part_invalid=enc_f['part_invalid'])
+                if 'p_valid' in enc_f:
+                    ret['p_valid'] = enc_f['p_valid']
+            return ret
+        raw_f, enc_f = net(z_fine, self.network)
         idx = order.long().clamp_(0, N_samples + N_importance - 1)   # a permutation unless depths are NaN
         take = lambda a, b: torch.gather(torch.cat([a, b], 1), 1, idx[..., None].expand(-1, -1, a.shape[-1]))  # noqa: E731
         raw_all = take(raw, raw_f)
@@ -345,7 +386,7 @@ class RayCaster(nn.Module):
 
     def render_pts_density(self, pts, kps, skts, bones, netchunk=1024 * 64, network=None):
         assert kps.shape[0] == 1, f'Assuming only one pose is provided, got {kps.shape[0]} instead'
-        eng = self._engine()
+        eng = self._engine(network=self.network_fine if self.two_net else None)     # the fine network, when there is one (:716-724)
         return eng.density(pts.reshape(-1, 1, 3), skts[:1], bones[:1], netchunk=int(netchunk))
 
     @torch.no_grad()
@@ -359,14 +400,15 @@ class RayCaster(nn.Module):
 
 
 class _GraphCache:
-    """One captured HIP graph per (chunk shape, sampling, engine state).  The engine's packed weights are part of the
-    captured pointers, so every graph is dropped when the engine has been refreshed with new parameter versions."""
+    """One captured HIP graph per (chunk shape, sampling, engine state).  The engines' packed weights are part of the
+    captured pointers, so every graph is dropped when any of the engines (coarse, and fine with a separate fine network) has been
+    refreshed with new parameter versions."""
 
     def __init__(self, max_graphs=8):
         self.max_graphs, self.engine_key, self.graphs = max_graphs, None, {}
 
-    def run(self, eng, key, chain, rb, skts_g, bones_g, cyls_g, cams):
-        state = (eng._packed_key, eng.mlp_mode)
+    def run(self, engines, key, chain, rb, skts_g, bones_g, cyls_g, cams):
+        state = tuple((eng._packed_key, eng.mlp_mode) for eng in engines)
         if self.engine_key != state:
             self.graphs.clear()
             self.engine_key = state

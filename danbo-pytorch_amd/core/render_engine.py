@@ -360,3 +360,51 @@ class DanboEngine:
                        z_sorted=z_all, sorted_idxs=order, raw_fine=raw_f, raw_sorted=raw_all,
                        count_coarse=ex["count"], count_fine=ex_f["count"], valid_bits=ex["valid_bits"])
         return ret
+
+    # ------------------------------------------------------------------ RayCaster.render_rays, single_net = False (eval)
+    def render_two_net(self, fine, rays_o, rays_d, skts, bones, cyls, cam_idx=None, N_samples=None, N_importance=None,
+                       chunk=4096, near_far=None, dense=False, keep=False):
+        """The hierarchical render of a caster with a separate fine network (reference raycasters.py:330-377): this engine's
+        network on the S coarse samples and their composite (rgb0 ...); the two-network pdf (is_only=False) for the Sf importance
+        depths; `fine` -- the fine network's engine -- on ALL S + Sf samples in sorted order, composited as they are: coarse and
+        fine raw are never merged.  The bounds are this (the coarse) engine's, as the reference's use_volume_near_far.
+
+        Each pass culls with its own network's volumes (the fine network's axis_scale is its own parameter: a mask from the coarse
+        boxes could drop fine samples inside a fine volume).  No rays of constants here: the fine pass reads z_sorted of every ray,
+        so every ray is resampled; lazy (dense=False, keep=False) still leaves the raw rows outside every volume unwritten, each
+        composite reading its own network's empty-space raw for them -- bit for bit the filled result."""
+        cfg = self.cfg
+        S = N_samples or cfg["N_samples"]
+        Sf = N_importance or cfg["N_importance"]
+        B = cfg["density_scale"]
+        self.refresh()
+        fine.refresh()
+        lazy = not dense and not keep
+        near, far = self.near_far(rays_o, rays_d, cyls, skts, 0.0, 1.0, chunk) if near_far is None else near_far
+        z = ops.coarse_samples(near, far, S)
+        # candidate bones over [near, far] -- coarse and importance depths both lie inside -- per network
+        masks = [None if dense else ops.ray_bone_mask(rays_o, rays_d, skts, e.align, e.axis_scale, near, far) for e in (self, fine)]
+        counts = torch.zeros(2, device=rays_o.device, dtype=torch.int32)
+        view = self.view_constants(rays_d, skts, cam_idx)
+        raw, ex = self.forward_samples(rays_o, rays_d, skts, bones, cam_idx, z=z, dense=dense, volumes=self.volumes(bones), view=view,
+                                       fill=not lazy, ray_mask=masks[0], count=counts[0:1])
+        bits, empty = (ex["valid_bits"], view[1]) if lazy else (None, None)
+        if S <= 64 and Sf <= 64:
+            out0, z_all, z_fine, order = ops.composite_importance(raw, z, rays_d, Sf, B, bits=bits, raw_empty=empty,
+                                                                  want_weights=keep, two_net=True)
+        else:
+            out0 = ops.composite(raw, z, rays_d, B, bits=bits, raw_empty=empty)
+            z_all, z_fine, order = ops.importance_samples(z, out0["weights"], Sf, two_net=True)
+        view_f = fine.view_constants(rays_d, skts, cam_idx)
+        raw_f, ex_f = fine.forward_samples(rays_o, rays_d, skts, bones, cam_idx, z=z_all, dense=dense, volumes=fine.volumes(bones),
+                                           view=view_f, fill=not lazy, ray_mask=masks[1], count=counts[1:2])
+        bits_f, empty_f = (ex_f["valid_bits"], view_f[1]) if lazy else (None, None)
+        out = ops.composite(raw_f, z_all, rays_d, B, bits=bits_f, raw_empty=empty_f)
+        ret = dict(rgb_map=out["rgb_map"], disp_map=out["disp_map"], acc_map=out["acc_map"], alpha=out["alpha"],
+                   T_i=out["weights"], rgb0=out0["rgb_map"], disp0=out0["disp_map"], acc0=out0["acc_map"],
+                   alpha0=out0["alpha"])
+        if keep:
+            ret.update(near=near, far=far, z_coarse=z, raw_coarse=raw, weights_coarse=out0["weights"], z_fine=z_fine,
+                       z_sorted=z_all, sorted_idxs=order, raw_fine=raw_f, count_coarse=ex["count"], count_fine=ex_f["count"],
+                       valid_bits=ex["valid_bits"], valid_bits_fine=ex_f["valid_bits"])
+        return ret

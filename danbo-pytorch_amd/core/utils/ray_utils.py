@@ -41,10 +41,10 @@ def sample_from_lineseg(near, far, N_lines, N_samples, perturb=0., lindisp=False
 
 
 def isample_from_lineseg(z_vals, weights, N_importance, det=False, pytest=False, is_only=False, alpha_base=0.01):
-    if not is_only:
-        raise NotImplementedError("two-network importance sampling (single_net=False) is out of scope")
+    """is_only=True: the single-network pdf (max filter + alpha_base); False: the two-network pdf, weights[..., 1:-1]
+    (reference :257-291).  alpha_base is the kernels' constant 0.01."""
     u = None if det else torch.rand(z_vals.shape[0], N_importance, device=z_vals.device)
-    z_all, z_fine, idx = ops.importance_samples(z_vals, weights.detach(), N_importance, u)
+    z_all, z_fine, idx = ops.importance_samples(z_vals, weights.detach(), N_importance, u, two_net=not is_only)
     return z_all, z_fine, idx
 
 

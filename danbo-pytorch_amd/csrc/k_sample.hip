@@ -944,7 +944,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 // ======================================================================================
 // importance sampling + merge
 // ======================================================================================
-// General fallback (any S): one thread per ray, the sorted_idx row doubles as cdf scratch.
+// General fallback (any S): one thread per ray, the sorted_idx row doubles as cdf scratch.  TWO: the two-network pdf
+// (pdf_weight, sample_math.hpp), here and in every importance kernel below.
+template <bool TWO>
 __global__ __launch_bounds__(64) void k_importance(const float* __restrict__ z, const float* __restrict__ weights,
                                                    int R, int S, int Sf, const float* __restrict__ u,
                                                    float* __restrict__ z_fine, float* __restrict__ z_sorted,
@@ -955,7 +957,7 @@ __global__ __launch_bounds__(64) void k_importance(const float* __restrict__ z, 
         float* zf = z_fine + (size_t)r * Sf;
         float* zs = z_sorted + (size_t)r * (S + Sf);
         int32_t* si = sorted_idx + (size_t)r * (S + Sf);
-        importance_ray(zr, weights + (size_t)r * S, S, Sf, u ? u + (size_t)r * Sf : nullptr, cdf, zf, zs, si);
+        importance_ray<TWO>(zr, weights + (size_t)r * S, S, Sf, u ? u + (size_t)r * Sf : nullptr, cdf, zf, zs, si);
         bool ascending = true;
         for (int i = 0; i + 1 < S; ++i) ascending = ascending && zr[i + 1] >= zr[i];
         if (u != nullptr || !ascending) {
@@ -984,7 +986,7 @@ __global__ __launch_bounds__(64) void k_importance(const float* __restrict__ z, 
 // from ranks -- two more binary searches when the draws are the sorted linspace (eval), broadcast compares for
 // random draws -- no sort, no scratch memory, every global access coalesced.
 //   zi / wi: this lane's coarse depth (INFINITY beyond S) and weight (0 beyond S)
-template <bool DET>
+template <bool DET, bool TWO = false>
 __device__ __forceinline__ void importance_wave(float zi, float wi, int r, int S, int Sf, const float* __restrict__ u,
                                                 int lane, float* __restrict__ z_fine, float* __restrict__ z_sorted,
                                                 int32_t* __restrict__ sorted_idx) {
@@ -993,7 +995,7 @@ __device__ __forceinline__ void importance_wave(float zi, float wi, int r, int S
     const float w1 = __shfl_down(wi, 1, 64), w2 = __shfl_down(wi, 2, 64);
     const float z1 = __shfl_down(zi, 1, 64);
     float dw = 0.f;
-    if (lane < nb) dw = add_rn(add_rn(mul_rn(0.5f, add_rn(fmaxf(wi, w1), fmaxf(w1, w2))), 0.01f), 1e-5f);
+    if (lane < nb) dw = pdf_weight<TWO>(wi, w1, w2);
     const float sum = wave_total(dw);
     const float inc = wave_scan_add(div_rn(dw, sum));  // pdf -> inclusive scan
     float cdf = __shfl_up(inc, 1, 64);                 // lane i: cdf[i], i in [0, ncdf)
@@ -1060,7 +1062,7 @@ __device__ __forceinline__ void importance_wave(float zi, float wi, int r, int S
     if (fact) { z_sorted[o + rank_f] = zf; sorted_idx[o + rank_f] = S + lane; }
 }
 
-template <bool DET>
+template <bool DET, bool TWO = false>
 __global__ __launch_bounds__(256) void k_importance_wave(const float* __restrict__ z, const float* __restrict__ weights,
                                                          int R, int S, int Sf, const float* __restrict__ u,
                                                          float* __restrict__ z_fine, float* __restrict__ z_sorted,
@@ -1072,7 +1074,7 @@ __global__ __launch_bounds__(256) void k_importance_wave(const float* __restrict
         const bool cact = lane < S;
         const float zi = cact ? z[(size_t)r * S + lane] : INFINITY;
         const float wi = cact ? weights[(size_t)r * S + lane] : 0.f;
-        importance_wave<DET>(zi, wi, r, S, Sf, u, lane, z_fine, z_sorted, sorted_idx);
+        importance_wave<DET, TWO>(zi, wi, r, S, Sf, u, lane, z_fine, z_sorted, sorted_idx);
     }
 }
 
@@ -1081,7 +1083,7 @@ __global__ __launch_bounds__(256) void k_importance_wave(const float* __restrict
 // frame.)  Same arithmetic as importance_wave: pdf, total and cdf by DPP scans (chunk after chunk, the carry added per chunk),
 // inverse CDF and ranks by binary searches -- in LDS instead of shuffles.
 constexpr int IMPB_MAX_S = 256;
-template <bool DET>
+template <bool DET, bool TWO = false>
 __global__ __launch_bounds__(256) void k_importance_wave_long(const float* __restrict__ z, const float* __restrict__ weights,
                                                               int R, int S, int Sf, const float* __restrict__ u,
                                                               float* __restrict__ z_fine, float* __restrict__ z_sorted,
@@ -1116,7 +1118,7 @@ __global__ __launch_bounds__(256) void k_importance_wave_long(const float* __res
             float dw = 0.f;
             if (c < nchunk && s0 < nb) {
                 const float w0 = s_w[s0], w1 = s_w[s0 + 1], w2 = s_w[s0 + 2];
-                dw = add_rn(add_rn(mul_rn(0.5f, add_rn(fmaxf(w0, w1), fmaxf(w1, w2))), 0.01f), 1e-5f);
+                dw = pdf_weight<TWO>(w0, w1, w2);
             }
             dwv[c] = dw;
             if (c < nchunk) {
@@ -1212,7 +1214,7 @@ __global__ __launch_bounds__(256) void k_importance_wave_long(const float* __res
 // coarse composite + importance resampling of a ray in one pass (S, Sf <= 64): the weights never leave the
 // wavefront's registers unless the caller asks for them.  Item i of the launch is the i-th listed ray (ray_list / ray_count:
 // k_flat_rays' list of the rays that are NOT rays of constants) or, without a list, ray scattered_ray(i).
-template <bool DET>
+template <bool DET, bool TWO = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_composite_importance(const float4* __restrict__ raw,
                                                               const float4* __restrict__ raw_empty,
                                                               const uint32_t* __restrict__ bits,
@@ -1280,7 +1282,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             if (alpha_out) alpha_out[m] = al;
         }
         if (lane == 0) composite_finish(st, r, rgb_map, disp, acc_out);
-        importance_wave<DET>(act ? zs : INFINITY, act ? w : 0.f, r, S, Sf, u, lane, z_fine, z_sorted, sorted_idx);
+        importance_wave<DET, TWO>(act ? zs : INFINITY, act ? w : 0.f, r, S, Sf, u, lane, z_fine, z_sorted, sorted_idx);
         cur = nxt; r = r_n; r_nxt = r_nn;
     }
 }
@@ -1502,6 +1504,7 @@ extern "C" int danbo_composite_rays_fwd(const float* raw, const float* raw_empty
                           stream);
 }
 
+template <bool TWO>
 static int importance_impl(const float* z, const float* weights, int R, int S, int Sf, const float* u, float* z_fine,
                            float* z_sorted, int32_t* sorted_idx, const int32_t* ray_list, const int32_t* ray_count, void* stream) {
     DANBO_CHECK_ARG(R > 0 && S >= 3 && Sf > 0);
@@ -1509,58 +1512,87 @@ static int importance_impl(const float* z, const float* weights, int R, int S, i
     DANBO_CHECK_ARG(ray_list == nullptr || (S > 64 && S <= IMPB_MAX_S && Sf <= 64));      // (the list: the long-ray kernel only)
     if (S <= 64 && Sf <= 64) {
         if (u)
-            hipLaunchKernelGGL(k_importance_wave<false>, dim3(stream_grid((long)R * 64, 256)), dim3(256), 0,
+            hipLaunchKernelGGL((k_importance_wave<false, TWO>), dim3(stream_grid((long)R * 64, 256)), dim3(256), 0,
                                (hipStream_t)stream, z, weights, R, S, Sf, u, z_fine, z_sorted, sorted_idx);
         else
-            hipLaunchKernelGGL(k_importance_wave<true>, dim3(stream_grid((long)R * 64, 256)), dim3(256), 0,
+            hipLaunchKernelGGL((k_importance_wave<true, TWO>), dim3(stream_grid((long)R * 64, 256)), dim3(256), 0,
                                (hipStream_t)stream, z, weights, R, S, Sf, u, z_fine, z_sorted, sorted_idx);
     } else if (S <= IMPB_MAX_S && Sf <= 64) {
         const dim3 grid(stream_grid((long)R * 64, 256));
         if (u)
-            hipLaunchKernelGGL(k_importance_wave_long<false>, grid, dim3(256), 0, (hipStream_t)stream, z, weights, R, S, Sf, u, z_fine,
+            hipLaunchKernelGGL((k_importance_wave_long<false, TWO>), grid, dim3(256), 0, (hipStream_t)stream, z, weights, R, S, Sf, u, z_fine,
                                z_sorted, sorted_idx, ray_scatter(R), ray_list, ray_count);
         else
-            hipLaunchKernelGGL(k_importance_wave_long<true>, grid, dim3(256), 0, (hipStream_t)stream, z, weights, R, S, Sf, u, z_fine,
+            hipLaunchKernelGGL((k_importance_wave_long<true, TWO>), grid, dim3(256), 0, (hipStream_t)stream, z, weights, R, S, Sf, u, z_fine,
                                z_sorted, sorted_idx, ray_scatter(R), ray_list, ray_count);
     } else {
-        hipLaunchKernelGGL(k_importance, dim3(stream_grid(R, 64)), dim3(64), 0, (hipStream_t)stream, z, weights, R, S, Sf,
+        hipLaunchKernelGGL(k_importance<TWO>, dim3(stream_grid(R, 64)), dim3(64), 0, (hipStream_t)stream, z, weights, R, S, Sf,
                            u, z_fine, z_sorted, sorted_idx);
     }
     DANBO_LAUNCH_RET();
 }
 extern "C" int danbo_importance_samples(const float* z, const float* weights, int R, int S, int Sf, const float* u,
                                          float* z_fine, float* z_sorted, int32_t* sorted_idx, void* stream) {
-    return importance_impl(z, weights, R, S, Sf, u, z_fine, z_sorted, sorted_idx, nullptr, nullptr, stream);
+    return importance_impl<false>(z, weights, R, S, Sf, u, z_fine, z_sorted, sorted_idx, nullptr, nullptr, stream);
 }
 extern "C" int danbo_importance_samples_rays(const float* z, const float* weights, int R, int S, int Sf, const float* u,
                                               float* z_fine, float* z_sorted, int32_t* sorted_idx, const int32_t* ray_list,
                                               const int32_t* ray_count, void* stream) {
-    return importance_impl(z, weights, R, S, Sf, u, z_fine, z_sorted, sorted_idx, ray_list, ray_count, stream);
+    return importance_impl<false>(z, weights, R, S, Sf, u, z_fine, z_sorted, sorted_idx, ray_list, ray_count, stream);
+}
+extern "C" int danbo_importance_samples_pdf(const float* z, const float* weights, int R, int S, int Sf, const float* u, int pdf,
+                                             float* z_fine, float* z_sorted, int32_t* sorted_idx, const int32_t* ray_list,
+                                             const int32_t* ray_count, void* stream) {
+    DANBO_CHECK_ARG(pdf == 0 || pdf == 1);
+    return pdf ? importance_impl<true>(z, weights, R, S, Sf, u, z_fine, z_sorted, sorted_idx, ray_list, ray_count, stream)
+               : importance_impl<false>(z, weights, R, S, Sf, u, z_fine, z_sorted, sorted_idx, ray_list, ray_count, stream);
 }
 
+template <bool TWO>
+static int composite_importance_impl(const float* raw, const float* raw_empty, const uint32_t* valid_bits, const float* z,
+                                     const float* rays_d, int R, int S, int Sf, float B, const float* noise, const float* u,
+                                     float* rgb_map, float* disp, float* acc, float* weights, float* alpha, float* z_fine,
+                                     float* z_sorted, int32_t* sorted_idx, const int32_t* ray_list, const int32_t* ray_count,
+                                     void* stream) {
+    DANBO_CHECK_ARG(R > 0 && S >= 3 && S <= 64 && Sf > 0 && Sf <= 64 && B > 0.f);
+    DANBO_CHECK_ARG(raw && z && rays_d && rgb_map && disp && acc && z_fine && z_sorted && sorted_idx);
+    DANBO_CHECK_ARG((valid_bits == nullptr) || (raw_empty != nullptr));
+    DANBO_CHECK_ARG((ray_list == nullptr) == (ray_count == nullptr));
+    static const int resident[2] = {resident_grid(k_composite_importance<false, TWO>, 1L << 40, 256),
+                                    resident_grid(k_composite_importance<true, TWO>, 1L << 40, 256)};
+    const dim3 grid((unsigned)std::min<long>(ceil_div((long)R * 64, 256), resident[u ? 0 : 1])), block(256);
+    const float4* r4 = reinterpret_cast<const float4*>(raw);
+    const float4* e4 = reinterpret_cast<const float4*>(raw_empty);
+    if (u)
+        hipLaunchKernelGGL((k_composite_importance<false, TWO>), grid, block, 0, (hipStream_t)stream, r4, e4, valid_bits, z, rays_d,
+                           R, S, Sf, B, noise, u, rgb_map, disp, acc, weights, alpha, z_fine, z_sorted, sorted_idx, ray_list, ray_count,
+                           ray_scatter(R));
+    else
+        hipLaunchKernelGGL((k_composite_importance<true, TWO>), grid, block, 0, (hipStream_t)stream, r4, e4, valid_bits, z, rays_d,
+                           R, S, Sf, B, noise, u, rgb_map, disp, acc, weights, alpha, z_fine, z_sorted, sorted_idx, ray_list, ray_count,
+                           ray_scatter(R));
+    DANBO_LAUNCH_RET();
+}
 extern "C" int danbo_composite_importance_fwd(const float* raw, const float* raw_empty, const uint32_t* valid_bits,
                                                const float* z, const float* rays_d, int R, int S, int Sf, float B,
                                                const float* noise, const float* u, float* rgb_map, float* disp,
                                                float* acc, float* weights, float* alpha, float* z_fine, float* z_sorted,
                                                int32_t* sorted_idx, const int32_t* ray_list, const int32_t* ray_count,
                                                void* stream) {
-    DANBO_CHECK_ARG(R > 0 && S >= 3 && S <= 64 && Sf > 0 && Sf <= 64 && B > 0.f);
-    DANBO_CHECK_ARG(raw && z && rays_d && rgb_map && disp && acc && z_fine && z_sorted && sorted_idx);
-    DANBO_CHECK_ARG((valid_bits == nullptr) || (raw_empty != nullptr));
-    DANBO_CHECK_ARG((ray_list == nullptr) == (ray_count == nullptr));
-    static const int resident[2] = {resident_grid(k_composite_importance<false>, 1L << 40, 256), resident_grid(k_composite_importance<true>, 1L << 40, 256)};
-    const dim3 grid((unsigned)std::min<long>(ceil_div((long)R * 64, 256), resident[u ? 0 : 1])), block(256);
-    const float4* r4 = reinterpret_cast<const float4*>(raw);
-    const float4* e4 = reinterpret_cast<const float4*>(raw_empty);
-    if (u)
-        hipLaunchKernelGGL(k_composite_importance<false>, grid, block, 0, (hipStream_t)stream, r4, e4, valid_bits, z, rays_d,
-                           R, S, Sf, B, noise, u, rgb_map, disp, acc, weights, alpha, z_fine, z_sorted, sorted_idx, ray_list, ray_count,
-                           ray_scatter(R));
-    else
-        hipLaunchKernelGGL(k_composite_importance<true>, grid, block, 0, (hipStream_t)stream, r4, e4, valid_bits, z, rays_d,
-                           R, S, Sf, B, noise, u, rgb_map, disp, acc, weights, alpha, z_fine, z_sorted, sorted_idx, ray_list, ray_count,
-                           ray_scatter(R));
-    DANBO_LAUNCH_RET();
+    return composite_importance_impl<false>(raw, raw_empty, valid_bits, z, rays_d, R, S, Sf, B, noise, u, rgb_map, disp, acc, weights,
+                                            alpha, z_fine, z_sorted, sorted_idx, ray_list, ray_count, stream);
+}
+extern "C" int danbo_composite_importance_pdf_fwd(const float* raw, const float* raw_empty, const uint32_t* valid_bits,
+                                                   const float* z, const float* rays_d, int R, int S, int Sf, float B,
+                                                   const float* noise, const float* u, int pdf, float* rgb_map, float* disp,
+                                                   float* acc, float* weights, float* alpha, float* z_fine, float* z_sorted,
+                                                   int32_t* sorted_idx, const int32_t* ray_list, const int32_t* ray_count,
+                                                   void* stream) {
+    DANBO_CHECK_ARG(pdf == 0 || pdf == 1);
+    return pdf ? composite_importance_impl<true>(raw, raw_empty, valid_bits, z, rays_d, R, S, Sf, B, noise, u, rgb_map, disp, acc,
+                                                 weights, alpha, z_fine, z_sorted, sorted_idx, ray_list, ray_count, stream)
+               : composite_importance_impl<false>(raw, raw_empty, valid_bits, z, rays_d, R, S, Sf, B, noise, u, rgb_map, disp, acc,
+                                                  weights, alpha, z_fine, z_sorted, sorted_idx, ray_list, ray_count, stream);
 }
 
 extern "C" int danbo_flat_rays(const float* t_lo, const uint32_t* ray_flat, int R, int S, int Sf, float* rgb0, float* disp0, float* acc0, float* weights0, float* alpha0, float* z_fine,

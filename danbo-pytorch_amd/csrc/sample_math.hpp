@@ -208,15 +208,27 @@ DANBO_HD bool bone_box_steps(const float* skt, const float* align, const float* 
     return hits == 2;
 }
 
-// ---- importance sampling of one ray (is_only pdf + inverse CDF + stable merge) --------
+// ---- pdf weight of importance bin i (core/utils/ray_utils.py:271-279 + sample_pdf's + 1e-5) ------------------------
+// TWO = false (one network, is_only):  0.5 (max(w_i, w_i+1) + max(w_i+1, w_i+2)) + 0.01 + 1e-5
+// TWO = true  (separate fine network):  w_i+1 + 1e-5
+// A compile-time choice: the single-network instantiations are the code they were before the two-network form existed.
+template <bool TWO>
+DANBO_HD float pdf_weight(float w0, float w1, float w2) {
+    if (TWO) return add_rn(w1, 1e-5f);
+    return add_rn(add_rn(mul_rn(0.5f, add_rn(fmaxf(w0, w1), fmaxf(w1, w2))), 0.01f), 1e-5f);
+}
+
+// ---- importance sampling of one ray (pdf + inverse CDF + stable merge) --------------------
 // core/utils/ray_utils.py:159-203,257-291.  z, w: [S]; u: [Sf] or NULL (linspace);
 // scratch cdf: [S-1] floats... caller provides `cdf` with room for S floats.
+// TWO: the pdf of the two-network mode (pdf_weight).
+template <bool TWO = false>
 DANBO_HD void importance_ray(const float* z, const float* w, int S, int Sf, const float* u, float* cdf,
                              float* z_fine, float* z_sorted, int32_t* sorted_idx) {
     const int nb = S - 2;  // number of pdf bins; bin edges are the S-1 midpoints
     float sum = 0.f;
     for (int i = 0; i < nb; ++i) {
-        const float dw = add_rn(add_rn(mul_rn(0.5f, add_rn(fmaxf(w[i], w[i + 1]), fmaxf(w[i + 1], w[i + 2]))), 0.01f), 1e-5f);
+        const float dw = pdf_weight<TWO>(w[i], w[i + 1], w[i + 2]);
         cdf[i + 1] = dw;
         sum = add_rn(sum, dw);
     }

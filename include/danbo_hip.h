@@ -39,7 +39,8 @@ extern "C" {
  * 8 = A-NeRF on the library's own kernels end to end (additive): danbo_anerf_view_consts_fwd / _bwd, danbo_anerf_train_step and its
  * building blocks; 9 = K3 in the 32x32x16 form (danbo_mlp32_pack, danbo_pe_mlp32_fwd: additive), danbo_view_consts' rgb_order 2;
  * danbo_render_frame runs it: DanboModel.mlp16 is a buffer packed by danbo_mlp32_pack (a caller of ABI 8 must re-pack); additive:
- * danbo_transform_batch_pts, danbo_optcodes_fwd (the reference's eager encoder helpers). */
+ * danbo_transform_batch_pts, danbo_optcodes_fwd (the reference's eager encoder helpers); danbo_importance_samples_pdf,
+ * danbo_composite_importance_pdf_fwd (the pdf of the two-network mode, single_net = False). */
 int danbo_abi_version(void);
 int danbo_device_info(int* cu_count, int* lds_bytes, char* arch, int arch_len);
 
@@ -335,6 +336,14 @@ int danbo_importance_samples(const float* z, const float* weights, int R, int S,
 int danbo_importance_samples_rays(const float* z, const float* weights, int R, int S, int Sf, const float* u,
                                   float* z_fine, float* z_sorted, int32_t* sorted_idx, const int32_t* ray_list,
                                   const int32_t* ray_count, void* stream);
+/* danbo_importance_samples_rays with a choice of pdf (additive in ABI 9).  pdf 0: the single-network pdf above
+ * (isample_from_lineseg(is_only=True)); pdf 1: the two-network pdf, isample_from_lineseg(is_only=False) of a caster with a
+ * separate fine network: bin i (between mid-points i and i+1) has weight weights[i+1] + 1e-5 -- no max filter, no alpha_base.
+ * Inverse CDF, merge and ranking are those of pdf 0; pdf 0 runs exactly the kernels danbo_importance_samples_rays runs.
+ * Any other pdf is DANBO_EINVAL.  ray_list / ray_count: as danbo_importance_samples_rays (both NULL: every ray). */
+int danbo_importance_samples_pdf(const float* z, const float* weights, int R, int S, int Sf, const float* u, int pdf,
+                                 float* z_fine, float* z_sorted, int32_t* sorted_idx, const int32_t* ray_list,
+                                 const int32_t* ray_count, void* stream);
 
 /* merge_samples (core/raycasters.py:745-761): out[r,i,:] = cat(a[r],b[r])[sorted_idx[r,i],:] */
 int danbo_merge_samples(const float* a /*[R,S,C]*/, const float* b /*[R,Sf,C]*/, const int32_t* sorted_idx,
@@ -352,6 +361,14 @@ int danbo_composite_importance_fwd(const float* raw /*[R,S,4]*/, const float* ra
                                    float* acc, float* weights, float* alpha, float* z_fine, float* z_sorted,
                                    int32_t* sorted_idx, const int32_t* ray_list /*[R] or NULL*/,
                                    const int32_t* ray_count /*[1] or NULL*/, void* stream);
+/* danbo_composite_importance_fwd with danbo_importance_samples_pdf's choice of pdf (additive in ABI 9): pdf 1 resamples with
+ * the two-network pdf, bit for bit danbo_composite_fwd followed by danbo_importance_samples_pdf(pdf = 1). */
+int danbo_composite_importance_pdf_fwd(const float* raw /*[R,S,4]*/, const float* raw_empty /*[R,4]*/,
+                                       const uint32_t* valid_bits /*[R,S]*/, const float* z, const float* rays_d, int R, int S,
+                                       int Sf, float B, const float* noise, const float* u, int pdf, float* rgb_map, float* disp,
+                                       float* acc, float* weights, float* alpha, float* z_fine, float* z_sorted,
+                                       int32_t* sorted_idx, const int32_t* ray_list /*[R] or NULL*/,
+                                       const int32_t* ray_count /*[1] or NULL*/, void* stream);
 
 /* Rays of constants (no reference counterpart; the values are the reference's).  ray_flat: the flags danbo_ray_bone_mask made
  * and danbo_bone_cull of the COARSE pass (same rays, depths, mask, interval) has passed on -- a set flag says the ray cannot
