@@ -48,7 +48,8 @@ constexpr int WAVE = 64;
 // persistent kernels size their grids from it.  256 on a full MI355X; partitioned (CPX / DPX) or harvested parts report less.
 // Development switches (fault bisection, stream-order experiments, A/B of a packing) read the environment only in a
 // -DDANBO_DEV_SWITCHES build (make DEV=1); the product build compiles every one of them to its default: no environment variable
-// changes what the shipped library computes or in which order it enqueues it.
+// changes what the shipped library computes or in which order it enqueues it.  (One switch is read in every build: k_assign16's
+// DANBO_A16_NOSKIP, which must not change a bit either -- the suite checks exactly that.)
 #ifdef DANBO_DEV_SWITCHES
 static inline int dev_env(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 #else

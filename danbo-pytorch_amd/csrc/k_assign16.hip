@@ -44,7 +44,7 @@ __host__ __device__ constexpr int a16_piece0(int j) {
     for (int i = 0; i < j; ++i) p += 2 * (a16_deg(i) + 1) + 4;
     return p;
 }
-static_assert(a16_piece0(J) == 236, "piece count");
+static_assert(a16_piece0(J) == 236, "piece count");   // (A16_PIECES)
 
 // ---------------------------------------------------------------------------------------------
 struct A16PackArgs {
@@ -53,32 +53,88 @@ struct A16PackArgs {
     const float* w1;    // [24][32][32]
 };
 
+// Range guard (the K2 analogue of k_mlp16's pack scales and DanboEngine._equalized), exact in powers of two.  The split loses
+// nothing where an operand's lo half is an fp16 NORMAL; a checkpoint whose assignment net is 1000x smaller than the seeded one
+// puts the weights' hi halves near and the lo halves deep inside fp16's subnormals (2^-25 absolute, ~1e-4 of a logit), one whose
+// layer-0 output reaches 1e5 overflows the split of relu(z0).  So per bone j:
+//   s0 = 2^k  puts the largest |adjw W0| of the bone's layer-0 terms into [2^13, 2^14)   (the MFMA accumulates s0 z0),
+//   s1 = 2^k  does the same for W1,
+//   r  = 2^k  ~ 1 / (RMS column norm of the layer-0 terms x 0.7): the B operand of layer 1 is r relu(z0) -- the size of the
+//             features, whatever the checkpoint's scale -- formed as relu(s0 z0) x (r / s0): one multiply per value,
+// and the bias of layer 0 is staged times s0, that of layer 1 times s1 r, w2 divided by s1 r: every product and sum of the three
+// layers is the unscaled one times a power of two, only the hi / lo halves differ.  The factors ride in the unused tail of the
+// packed buffer (236 of its 256 pieces carry fragments): [24][4] floats {s0, r / s0, s1 r, 1 / (s1 r)} at A16_FAC_OFFSET.
+constexpr int A16_PIECES = 236;
+constexpr size_t A16_FAC_OFFSET = (size_t)A16_PIECES * 1024;       // bytes
+constexpr int A16_SCALE_EXP_MAX = 40;    // |log2| of a factor: products stay far from fp32's ends
+
+__device__ __forceinline__ int a16_exp_to(float m, int target) {     // k with m 2^k in [2^target, 2^(target+1)); 0 for m = 0, inf, NaN
+    if (!(m > 0.f) || !(m < INFINITY)) return 0;
+    int e;
+    frexpf(m, &e);                       // m in [2^(e-1), 2^e)
+    return min(max(target - (e - 1), -A16_SCALE_EXP_MAX), A16_SCALE_EXP_MAX);
+}
+
+// one workgroup per bone: the factors from its matrices, then its 2 (deg + 1) + 4 pieces; workgroup 0 also clears the rest of the tail
 __global__ __launch_bounds__(256) void k_assign16_pack(A16PackArgs a, _Float16* __restrict__ packed) {
-    const int total = A16_NCHUNK * (A16_CHUNK / 2);
-    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
-        const int piece = idx >> 9, lane = (idx >> 3) & 63, e = idx & 7;
+    __shared__ float s_red[3][256];
+    __shared__ float s_fac[4];
+    const int j = blockIdx.x, tid = threadIdx.x;
+    const int nq = a16_deg(j) + 1, n0 = 2 * nq;
+    float m0 = 0.f, m1 = 0.f, ss = 0.f;
+    for (int i = tid; i < nq * FEAT * 32; i += 256) {
+        const int q = i / (FEAT * 32), r = i - q * (FEAT * 32);
+        const int jp = a16_nb(j, q);
+        const float w = a.adjw[j * J + jp] * a.w0[(size_t)jp * FEAT * 32 + r];
+        m0 = fmaxf(m0, fabsf(w));
+        ss = fmaf(w, w, ss);
+    }
+    for (int i = tid; i < 32 * 32; i += 256) m1 = fmaxf(m1, fabsf(a.w1[(size_t)j * 32 * 32 + i]));
+    s_red[0][tid] = m0; s_red[1][tid] = m1; s_red[2][tid] = ss;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) {
+            s_red[0][tid] = fmaxf(s_red[0][tid], s_red[0][tid + w]);
+            s_red[1][tid] = fmaxf(s_red[1][tid], s_red[1][tid + w]);
+            s_red[2][tid] += s_red[2][tid + w];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const int k0 = a16_exp_to(s_red[0][0], 13), k1 = a16_exp_to(s_red[1][0], 13);
+        const float gain = sqrtf(s_red[2][0] * (1.0f / 32.0f)) * 0.7f;
+        const int kr = (gain > 0.f && gain < INFINITY) ? min(max(-(int)rintf(log2f(gain)), -A16_SCALE_EXP_MAX), A16_SCALE_EXP_MAX) : 0;
+        s_fac[0] = ldexpf(1.0f, k0);
+        s_fac[1] = ldexpf(1.0f, k1);
+        float* fac = reinterpret_cast<float*>(packed + A16_FAC_OFFSET / 2) + 4 * j;
+        fac[0] = ldexpf(1.0f, k0);
+        fac[1] = ldexpf(1.0f, kr - k0);
+        fac[2] = ldexpf(1.0f, k1 + kr);
+        fac[3] = ldexpf(1.0f, -(k1 + kr));
+    }
+    __syncthreads();
+    const float s0 = s_fac[0], s1 = s_fac[1];
+    _Float16* dst = packed + (size_t)a16_piece0(j) * 512;
+    for (int i = tid; i < (n0 + 4) * 512; i += 256) {
+        const int local = i >> 9, lane = (i >> 3) & 63, e = i & 7;
         const int n = lane & 31, h = lane >> 5;
+        const int hl = local & 1;
         float w = 0.f;
-        int hl = 0;
-        if (piece < 236) {
-            int j = 0;
-            while (j + 1 < J && a16_piece0(j + 1) <= piece) ++j;
-            const int local = piece - a16_piece0(j);
-            const int n0 = 2 * (a16_deg(j) + 1);
-            hl = local & 1;
-            if (local < n0) {  // layer 0, neighbour q
-                const int jp = a16_nb(j, local >> 1);
-                const int k = 8 * h + e;
-                if (k < FEAT) w = a.adjw[j * J + jp] * a.w0[((size_t)jp * FEAT + k) * 32 + n];
-            } else {  // layer 1, k-step ks
-                const int ks = (local - n0) >> 1;
-                const int c = 8 * (2 * ks + (e >> 2)) + 4 * h + (e & 3);
-                w = a.w1[((size_t)j * 32 + c) * 32 + n];
-            }
+        if (local < n0) {  // layer 0, neighbour q
+            const int jp = a16_nb(j, local >> 1);
+            const int k = 8 * h + e;
+            if (k < FEAT) w = a.adjw[j * J + jp] * a.w0[((size_t)jp * FEAT + k) * 32 + n];
+            w *= s0;
+        } else {  // layer 1, k-step ks
+            const int ks = (local - n0) >> 1;
+            const int c = 8 * (2 * ks + (e >> 2)) + 4 * h + (e & 3);
+            w = a.w1[((size_t)j * 32 + c) * 32 + n] * s1;
         }
         const _Float16 hi = (_Float16)w;
-        packed[idx] = hl ? (_Float16)(w - (float)hi) : hi;
+        dst[i] = hl ? (_Float16)(w - (float)hi) : hi;
     }
+    if (j == 0)
+        for (size_t i = A16_FAC_OFFSET / 2 + 4 * J * 2 + tid; i < (size_t)A16_NCHUNK * A16_CHUNK / 2; i += 256) packed[i] = (_Float16)0.f;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -97,7 +153,7 @@ struct A16Args {
     const int32_t* count;
     int n_cap;
     const char* packed;
-    const float* b0;  // [32]
+    const float* b0;  // [32]        (staged per bone times the pack's range factors, see k_assign16_pack)
     const float* b1;  // [24][32]
     const float* w2;  // [24][32]
     const float* b2;  // [24]
@@ -111,8 +167,8 @@ struct A16Args {
 };
 
 // per bone: neighbours (self first), number of layer-0 terms, first 1-KB piece of the packed stream
-constexpr int A16_NBI = 8;        // ints per bone: nb[0..4], nq = deg + 1, piece0, pad
-constexpr int A16_TABLE_FLOATS = 32 + J * 32 + J * 32 + J + J * 16 + J * 4 + 8 /*pad*/ + J * VOL + J * 16 + J * A16_NBI + J * 4 + J;
+constexpr int A16_NBI = 8;        // ints per bone: nb[0..4], nq = deg + 1, piece0, the bits of r / s0 (k_assign16_pack)
+constexpr int A16_TABLE_FLOATS = J * 32 + J * 32 + J * 32 + J + J * 16 + J * 4 + 8 /*pad*/ + J * VOL + J * 16 + J * A16_NBI + J * 4 + J;
 constexpr int A16_LDS_BYTES = (A16_TABLE_FLOATS * 4 + 15) & ~15;
 constexpr int A16_TICKETS_AHEAD = 4;   // draws of a workgroup that come back without a tile: the one that ends it + three in its pipeline
 
@@ -192,9 +248,9 @@ __device__ __forceinline__ void a16_split8(const float* v, half8& hi, half8& lo)
 template <bool TRAIN>
 __global__ __launch_bounds__(256, 2) void k_assign16(A16Args a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* s_b0 = reinterpret_cast<float*>(smem);                          // [32]
-    float* s_b1 = s_b0 + 32;                                               // [24][32]
-    float* s_w2 = s_b1 + J * 32;                                           // [24][32]
+    float* s_b0 = reinterpret_cast<float*>(smem);                          // [24][32]  b0 s0 of each bone
+    float* s_b1 = s_b0 + J * 32;                                           // [24][32]  b1 s1 r
+    float* s_w2 = s_b1 + J * 32;                                           // [24][32]  w2 / (s1 r)
     float* s_b2 = s_w2 + J * 32;                                           // [24]
     float* s_align = s_b2 + J;                                             // [24][16]
     float* s_scale = s_align + J * 16;                                     // [24][4]
@@ -206,8 +262,13 @@ __global__ __launch_bounds__(256, 2) void k_assign16(A16Args a) {
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int m = lane & 31, hh = lane >> 5;
-    if (tid < 32) s_b0[tid] = a.b0[tid];
-    for (int i = tid; i < J * 32; i += 256) { s_b1[i] = a.b1[i]; s_w2[i] = a.w2[i]; }
+    const float* fac = reinterpret_cast<const float*>(a.packed + A16_FAC_OFFSET);      // the pack's range factors (powers of two)
+    for (int i = tid; i < J * 32; i += 256) {
+        const float* f = fac + 4 * (i >> 5);
+        s_b0[i] = a.b0[i & 31] * f[0];
+        s_b1[i] = a.b1[i] * f[2];
+        s_w2[i] = a.w2[i] * f[3];
+    }
     if (tid < J) s_b2[tid] = a.b2[tid];
     for (int i = tid; i < J * 16; i += 256) s_align[i] = a.align[i];
     for (int i = tid; i < J * 4; i += 256) {
@@ -222,7 +283,7 @@ __global__ __launch_bounds__(256, 2) void k_assign16(A16Args a) {
                 for (int q = 0; q < 5; ++q) s_nbi[jj * A16_NBI + q] = a16_nb(jj, q) < 0 ? jj : a16_nb(jj, q);
                 s_nbi[jj * A16_NBI + 5] = a16_deg(jj) + 1;
                 s_nbi[jj * A16_NBI + 6] = a16_piece0(jj);
-                s_nbi[jj * A16_NBI + 7] = 0;
+                s_nbi[jj * A16_NBI + 7] = __float_as_int(fac[4 * jj + 1]);
             }
     }
     __syncthreads();
@@ -395,7 +456,7 @@ __global__ __launch_bounds__(256, 2) void k_assign16(A16Args a) {
             f32x16 acc;
 #pragma unroll
             for (int jj = 0; jj < 4; ++jj) {
-                const float4 b = *reinterpret_cast<const float4*>(s_b0 + 8 * jj + 4 * hh);
+                const float4 b = *reinterpret_cast<const float4*>(s_b0 + j * 32 + 8 * jj + 4 * hh);
                 acc[4 * jj] = b.x; acc[4 * jj + 1] = b.y; acc[4 * jj + 2] = b.z; acc[4 * jj + 3] = b.w;
             }
             // ---- features of the bone and its tree neighbours ----
@@ -469,10 +530,11 @@ __global__ __launch_bounds__(256, 2) void k_assign16(A16Args a) {
                 }
             }
             stamp(200 + j);
-            // ---- relu -> layer-1 B fragments ----
+            // ---- relu -> layer-1 B fragments: acc = s0 z0, the operand r relu(z0) (k_assign16_pack) ----
+            const float c0 = __int_as_float(__builtin_amdgcn_readfirstlane(s_nbi[j * A16_NBI + 7]));
             float v[16];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = fmaxf(acc[r], 0.f);
+            for (int r = 0; r < 16; ++r) v[r] = fmaxf(acc[r], 0.f) * c0;
             half8 zh[2], zl[2];
             a16_split8(v, zh[0], zl[0]);
             a16_split8(v + 8, zh[1], zl[1]);
@@ -529,8 +591,10 @@ __global__ __launch_bounds__(256, 2) void k_assign16(A16Args a) {
 using namespace danbo;
 
 static long long* g_a16_trace = nullptr;
+// DANBO_A16_NOSKIP=1: evaluate every neighbour pair.  Read in every build (the one exception to common.hpp's dev switches): the
+// skip claims to change no bit, and tests/test_gpu_assign16.py holds the shipped kernel to that against a process run with it.
 static int a16_no_skip() {
-    static const int v = dev_env("DANBO_A16_NOSKIP", 0);
+    static const int v = [] { const char* e = getenv("DANBO_A16_NOSKIP"); return e ? atoi(e) : 0; }();
     return v;
 }
 /* dev tool: a buffer of 256 int64 that receives (tag, s_memtime) stamps of one wavefront of k_assign16 (tags: 0 tile start, 1 inputs
@@ -543,7 +607,7 @@ extern "C" int danbo_assign16_set_trace(void* buf) {
 extern "C" int danbo_assign16_pack(const float* w0, const float* adjw, const float* w1, void* packed16, void* stream) {
     DANBO_CHECK_ARG(w0 && adjw && w1 && packed16);
     A16PackArgs a = {w0, adjw, w1};
-    hipLaunchKernelGGL(k_assign16_pack, dim3(512), dim3(256), 0, (hipStream_t)stream, a, reinterpret_cast<_Float16*>(packed16));
+    hipLaunchKernelGGL(k_assign16_pack, dim3(J), dim3(256), 0, (hipStream_t)stream, a, reinterpret_cast<_Float16*>(packed16));
     DANBO_LAUNCH_RET();
 }
 

@@ -173,7 +173,8 @@ int danbo_assign16_set_trace(void* buf);
 
 /* K1b + K2, fast variant (csrc/k_assign16.hip): same contract as danbo_gather_assign_blend_fwd with the
  * two per-bone GEMMs on fp16 hi/lo-split MFMAs (fp32 accumulate) and the skeleton adjacency folded
- * into the layer-0 weights by danbo_assign16_pack (w0 [24,15,32], adjw [24,24], w1 [24,32,32]). */
+ * into the layer-0 weights by danbo_assign16_pack (w0 [24,15,32], adjw [24,24], w1 [24,32,32]); the pack also writes the
+ * power-of-two range factors of each bone into the buffer's unused tail, which the kernel applies to b0, b1 and w2. */
 #define DANBO_ASSIGN16_PACKED_BYTES 262144
 int danbo_assign16_pack(const float* w0, const float* adjw, const float* w1, void* packed16, void* stream);
 int danbo_gather_assign_blend16_fwd(const float* rays_o, const float* rays_d, const float* z, const float* pts,

@@ -105,3 +105,23 @@ def philox_stream_words(seed, counter, n_quads, stream):
     idx = (np.uint64(counter) + np.arange(n_quads, dtype=np.uint64))
     ctr = np.stack([idx & np.uint64(0xFFFFFFFF), idx >> np.uint64(32), np.full(n_quads, stream, np.uint64), np.zeros(n_quads, np.uint64)], 1)
     return philox4x32_10(ctr, (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF))
+
+
+# ---- float64 arbiter of K2 (the assignment GNN + masked sigmoid + blend, k_assign / k_assign16): danbo_oracle.assignment_logits
+# and blend restated with every product and sum in float64, on the fp32 part_feat of the oracle's gather.  Test code only.
+def assignment_f64(sd, part_feat):
+    """MixGNN (gnn_backbone.py:567-591,602-629) in float64: part_feat [M,24,15] -> logits [M,24]"""
+    d = lambda k: np.asarray(sd["prob_linears.layers." + k], dtype=np.float64)      # noqa: E731
+    f = np.asarray(part_feat, dtype=np.float64).transpose(1, 0, 2)                    # [24, M, 15]: one matmul per bone
+    adjw = d("0.adj_w")[0] * d("0.adj")[0]
+    y = np.tensordot(adjw, np.matmul(f, d("0.lin.weight")), axes=(1, 0)) + d("0.bias").reshape(1, 1, -1)
+    y = np.maximum(y, 0.0)
+    y = np.maximum(np.matmul(y, d("1.weight")) + d("1.bias").reshape(24, 1, -1), 0.0)
+    return (np.matmul(y, d("2.weight")) + d("2.bias").reshape(24, 1, -1))[..., 0].T
+
+
+def blend_f64(part_feat, logits, valid):
+    """DANBO.sigmoid + blend (danbo.py:299-300,406-415) in float64 -> p [M,24], h [M,15]"""
+    with np.errstate(over="ignore"):        # exp(-logit) of a logit below -709: inf, p = -0.001 as it should
+        p = (1.002 / (1.0 + np.exp(-np.asarray(logits, dtype=np.float64))) - 0.001) * np.asarray(valid, dtype=np.float64)
+    return p, (np.asarray(part_feat, dtype=np.float64) * p[..., None]).sum(-2)

@@ -807,3 +807,45 @@ def test_loss_terms_are_snapshotted_at_the_first_look_and_refuse_a_late_one():
     trainer.train_batch(b, i=9, global_step=9, sync_stats=False)
     trainer.train_batch(b, i=10, global_step=10, sync_stats=False)
     assert np.isfinite(float(loss_d['total_loss'])) and len(loss_d) >= 3
+
+
+@pytest.mark.parametrize("case", ["prob_linears_x1e-3", "prob_layer0_x6e4"])
+def test_fused_step_with_an_assignment_net_outside_fp16_range(case):
+    """The forward of the fused step evaluates the assignment net on K2's fp16-split kernel (danbo_gather_assign_blend16_train):
+    an assignment net 1000x smaller than the seeded one, or one whose layer-0 output reaches ~1e5 (weights and bias x 6e4, layer 1
+    x 1/6e4) -- the same function at another scale -- must train as the float64 reference does (oracle/torch_f64_train.py), the
+    soft-softmax loss (the assignment mass of every row) included."""
+    f0, f1 = {"prob_linears_x1e-3": (1e-3, 1e-3), "prob_layer0_x6e4": (6e4, 1.0 / 6e4)}[case]
+
+    def model_edit(caster):
+        p = dict(caster.network.named_parameters())
+        a = "prob_linears.layers."
+        with torch.no_grad():
+            for k, f in (("0.lin.weight", f0), ("0.bias", f0), ("1.weight", f1), ("1.bias", f0 * f1), ("2.weight", 1.0 / (f0 * f1))):
+                p[a + k].copy_((p[a + k].double() * f).float())
+
+    g, args, caster, trainer, eng, out = fused_step("danbo_perfcap_train", model_edit=model_edit)
+    assert float(dict(caster.network.named_parameters())["prob_linears.layers.0.lin.weight"].abs().max()) > (1e3 if f0 > 1 else 0.0)
+    b64 = batch_of(g)
+    R64, G64 = b64["rays_o"].shape[0], int(b64["N_uniques"])
+    samp = _fused_sampling(eng, R64, G64, int(g["N_samples"]), int(g["N_importance"]))
+    samp.update(acc0=out["acc0"], acc_map=out["acc_map"])
+    r64 = _f64_reference(g, args, caster, b64, samp)
+    assert torch.isfinite(out["loss"]).all() and torch.isfinite(eng.flat_g).all()
+    R, St = out["rgb_map"].shape[0], out["alpha"].shape[1]
+    ls = out["loss"].cpu().numpy().astype(np.float64)
+    ours = {"rgb_loss": ls[0], "rgb_loss0": ls[1], "soft_softmax_loss": ls[2] * args.soft_softmax_loss_coef / (R * St)}
+    assert r64["loss"]["soft_softmax_loss"] > 0
+    for k, v in ours.items():
+        ref = r64["loss"][k]
+        print(case, k, v, "float64", ref, "rel", abs(v - ref) / abs(ref))
+        assert abs(v - ref) <= F64_BOUND * abs(ref), (k, v, ref)
+    worst, name = 0.0, ""
+    for n, p in caster.network.named_parameters():
+        t = r64["grads"][n]
+        scale = float(np.abs(t).max())
+        d = float(np.abs(p.grad.detach().cpu().numpy().astype(np.float64) - t).max())
+        if d / (scale + 1e-30) > worst:
+            worst, name = d / (scale + 1e-30), n
+        assert d <= F64_BOUND * scale + 1.5 * r64["bracket"][n] + 1e-9, (n, d, scale, r64["bracket"][n])
+    print(case, "worst gradient deviation from float64 (of the tensor's max)", worst, "in", name)

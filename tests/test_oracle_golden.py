@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import danbo_oracle as o
-from helpers import golden, oracle_for, max_err, rel_err, raw_err
+from helpers import golden, oracle_for, max_err, rel_err, raw_err, assignment_f64, blend_f64
 
 
 @pytest.fixture(scope="module")
@@ -77,6 +77,22 @@ def test_assignment_and_blend(stages):
     assert max_err(e["confd"], g["confd"]) < 1e-5
     assert max_err(e["agg_p"], g["agg_p"]) < 2e-6
     assert max_err(e["density_inputs"], g["density_inputs"]) < 2e-4  # sin(32 h) amplifies 1e-6
+
+
+def test_float64_assignment_arbiter_agrees_with_the_golden_and_the_oracle(stages):
+    """The float64 restatement of MixGNN + masked sigmoid + blend (helpers.assignment_f64 / blend_f64) that the K2 kernel tests
+    measure against: on the oracle's fp32 gather it agrees with the reference's logits and with the oracle's h at fp32 round-off
+    (measured 8.1e-8 and 4.4e-8) -- an arbiter that drifted from the graph would show here first."""
+    g, orc, ret = stages
+    pf = g["part_feat"].reshape(-1, 24, 15)
+    valid = ~g["invalid"].reshape(-1, 24).astype(bool)
+    logits = assignment_f64(orc.sd, pf)
+    assert np.abs(g["confd"]).max() > 0.1 and valid.sum(-1).max() >= 2
+    assert max_err(logits, g["confd"].reshape(-1, 24)) < 5e-7
+    p, h = blend_f64(pf, logits, valid)
+    assert max_err(p, g["agg_p"]) < 5e-7
+    assert max_err(h, ret["enc"]["h"]) < 2e-7
+    assert np.abs(h).max() > 0.1
 
 
 def test_view_inputs(stages):
