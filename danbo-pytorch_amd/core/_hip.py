@@ -42,6 +42,7 @@ SIGNATURES = {
     "danbo_pe_mlp_fwd": [P, P, P, I, I, P, POINTER(c_void_p), P, P, P, P, P, P, P, P, P],
     "danbo_fill_raw": [P, I, I, P, P],
     "danbo_composite_rays_fwd": [P, P, P, P, P, I, I, F, P, P, P, P, P, P, P, P, P],
+    "danbo_composite_rays_fwd_act": [P, P, P, P, P, I, I, F, P, P, P, P, P, P, P, P, I, F, P],
     "danbo_importance_samples_rays": [P, P, I, I, I, P, P, P, P, P, P, P],
     "danbo_composite_fwd": [P, P, P, I, I, F, P, P, P, P, P, P, P],
     "danbo_composite_bwd": [P, P, P, I, I, F, P, P, P, P, P],
@@ -51,7 +52,9 @@ SIGNATURES = {
     "danbo_merge_samples": [P, P, P, I, I, I, I, P, P],
     "danbo_composite_importance_fwd": [P, P, P, P, P, I, I, I, F, P, P, P, P, P, P, P, P, P, P, P, P, P],
     "danbo_composite_importance_pdf_fwd": [P, P, P, P, P, I, I, I, F, P, P, I, P, P, P, P, P, P, P, P, P, P, P],
+    "danbo_composite_importance_pdf_fwd_act": [P, P, P, P, P, I, I, I, F, P, P, I, P, P, P, P, P, P, P, P, P, P, I, F, P],
     "danbo_composite_merged_fwd": [P, P, P, P, P, P, P, P, I, I, I, F, P, P, P, P, P, P, P, P, P, P],
+    "danbo_composite_merged_fwd_act": [P, P, P, P, P, P, P, P, I, I, I, F, P, P, P, P, P, P, P, P, P, I, F, P],
     "danbo_flat_rays": [P, P, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, P],
     "danbo_anerf_encode_fwd": [P, P, P, P, I, I, I, P, P, P, F, I, c_long, I, P, P, P],
     "danbo_anerf_encode_compact": [P, P, P, P, I, I, I, P, P, P, F, c_long, I, P, P, P],
@@ -68,8 +71,10 @@ SIGNATURES = {
     "danbo_linear16_fwd_color": [P, I, P, P, I, I, P, P, P, P, I, I, I, I, P, P, P, P],
     "danbo_render_frame_workspace": [I, I, I, I, I, I],
     "danbo_render_frame": [P, P, I, I, P, P, c_size_t, P],
+    "danbo_render_frame_act": [P, P, I, I, P, P, c_size_t, I, F, P],
     # ---- training step
     "danbo_composite_bwd_lazy": [P, P, P, P, P, I, I, F, P, P, P, P, P],
+    "danbo_composite_bwd_lazy_act": [P, P, P, P, P, I, I, F, P, P, P, P, I, F, P],
     "danbo_dw16_scratch_floats": [P, I, I],
     "danbo_dw16": [P, I, I, P, I, P, P],
     "danbo_gather_assign_blend16_train": [P, P, P, I, I, I, P, P, P, P, P, P, P, P, I, P, P, P, P, P, P, P, P],

@@ -177,16 +177,17 @@ class AnerfEngine:
         S = N_samples or cfg["N_samples"]
         Sf = N_importance or cfg["N_importance"]
         B = cfg["density_scale"]
+        act = ops.density_act(cfg.get("density_act"))     # (RayCaster._engines sets it per call, as density_scale)
         self.refresh()
         near, far = self.near_far(rays_o, rays_d, cyls, skts, 0.0, 1.0, chunk) if near_far is None else near_far
         z = ops.coarse_samples(near, far, S)
         C = self.view_constants(rays_d, skts)
         raw = self.forward_samples(rays_o, rays_d, skts, cam_idx, z=z, view=C)
-        out0 = ops.composite(raw, z, rays_d, B)
+        out0 = ops.composite(raw, z, rays_d, B, act=act)
         z_all, z_fine, order = ops.importance_samples(z, out0["weights"], Sf)
         raw_f = self.forward_samples(rays_o, rays_d, skts, cam_idx, z=z_fine, view=C)
         raw_all = ops.merge_samples(raw, raw_f, order)
-        out = ops.composite(raw_all, z_all, rays_d, B)
+        out = ops.composite(raw_all, z_all, rays_d, B, act=act)
         ret = dict(rgb_map=out["rgb_map"], disp_map=out["disp_map"], acc_map=out["acc_map"], alpha=out["alpha"],
                    T_i=out["weights"], rgb0=out0["rgb_map"], disp0=out0["disp_map"], acc0=out0["acc_map"],
                    alpha0=out0["alpha"])
@@ -204,15 +205,16 @@ class AnerfEngine:
         S = N_samples or cfg["N_samples"]
         Sf = N_importance or cfg["N_importance"]
         B = cfg["density_scale"]
+        act = ops.density_act(cfg.get("density_act"))     # (RayCaster._engines sets it per call, as density_scale)
         self.refresh()
         fine.refresh()
         near, far = self.near_far(rays_o, rays_d, cyls, skts, 0.0, 1.0, chunk) if near_far is None else near_far
         z = ops.coarse_samples(near, far, S)
         raw = self.forward_samples(rays_o, rays_d, skts, cam_idx, z=z, view=self.view_constants(rays_d, skts))
-        out0 = ops.composite(raw, z, rays_d, B)
+        out0 = ops.composite(raw, z, rays_d, B, act=act)
         z_all, z_fine, order = ops.importance_samples(z, out0["weights"], Sf, two_net=True)
         raw_f = fine.forward_samples(rays_o, rays_d, skts, cam_idx, z=z_all, view=fine.view_constants(rays_d, skts))
-        out = ops.composite(raw_f, z_all, rays_d, B)
+        out = ops.composite(raw_f, z_all, rays_d, B, act=act)
         ret = dict(rgb_map=out["rgb_map"], disp_map=out["disp_map"], acc_map=out["acc_map"], alpha=out["alpha"],
                    T_i=out["weights"], rgb0=out0["rgb_map"], disp0=out0["disp_map"], acc0=out0["acc_map"],
                    alpha0=out0["alpha"])

@@ -21,7 +21,7 @@ _FLAGS = [
     ("N_samples", int, 64), ("N_importance", int, 0), ("perturb", float, 1.0), ("use_viewdirs", bool, False),
     ("i_embed", int, 0), ("multires", int, 10), ("multires_views", int, 4), ("multires_bones", int, 0),
     ("raw_noise_std", float, 0.0), ("ray_noise_std", float, 0.0), ("render_factor", int, 0),
-    ("nerf_type", str, "nerf"), ("density_type", str, "relu"), ("lindisp", bool, False),
+    ("nerf_type", str, "nerf"), ("density_type", str, "relu"), ("softplus_shift", float, 1.0), ("lindisp", bool, False),
     ("gnn_concat", bool, False), ("adj_self_one", bool, False), ("gnn_backbone", str, "PoolPNGCN"),
     ("node_W", int, 32), ("gcn_D", int, 4), ("gcn_fc_D", int, 1), ("gcn_sep_bias", bool, False),
     ("no_adj", bool, False), ("init_adj_w", float, 0.05), ("aggregate_dim", int, None),

@@ -4,7 +4,8 @@ torch.library.custom_op with register_autograd"), so that a caller -- the refere
 
     torch.ops.danbo.pose_volumes(bones, L_graph, params)                  rot6d + PE + FactorizeGNN (reference core/networks/gnn_backbone.py:683-704)
         -> volumes [G,24,240] (+ the adjoint's scratch)                  backward: danbo_pose_volumes_bwd -> every parameter's gradient
-    torch.ops.danbo.composite(raw, z, rays_d, B, noise)                  NeRF.raw2outputs (reference core/networks/nerf.py:281-347)
+    torch.ops.danbo.composite(raw, z, rays_d, B, noise,                  NeRF.raw2outputs (reference core/networks/nerf.py:281-347)
+                              density_type="relu", softplus_shift=0.)     with act_fn = relu or softplus(x - shift) (raycasters.py:192-200)
         -> rgb_map, disp_map, acc_map, weights, alpha                     backward: danbo_composite_bwd (d rgb_map, d acc_map -> d raw)
     torch.ops.danbo.bone_gather(volumes, axis_scale, pts, skts, align, rows)
         -> part_feat [n,24,15]                                            FactorizeGNN.sample_from_volume (gnn_backbone.py:787-828)
@@ -41,14 +42,15 @@ def _p(t):
 
 # ------------------------------------------------------------------------------------------------------------------ composite
 @torch.library.custom_op("danbo::composite", mutates_args=())
-def composite(raw: torch.Tensor, z: torch.Tensor, rays_d: torch.Tensor, B: float,
-              noise: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    out = ops.composite(raw, z, rays_d, B, noise)
+def composite(raw: torch.Tensor, z: torch.Tensor, rays_d: torch.Tensor, B: float, noise: Optional[torch.Tensor],
+              density_type: str = "relu",
+              softplus_shift: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    out = ops.composite(raw, z, rays_d, B, noise, act=(density_type, softplus_shift))
     return out["rgb_map"], out["disp_map"], out["acc_map"], out["weights"], out["alpha"]
 
 
 @composite.register_fake
-def _(raw, z, rays_d, B, noise):
+def _(raw, z, rays_d, B, noise, density_type="relu", softplus_shift=0.0):
     R, S = z.shape
     f = lambda *s: raw.new_empty(s, dtype=torch.float32)  # noqa: E731
     return f(R, 3), f(R), f(R), f(R, S), f(R, S)
@@ -56,10 +58,17 @@ def _(raw, z, rays_d, B, noise):
 
 @torch.library.custom_op("danbo::composite_bwd", mutates_args=())
 def composite_bwd(raw: torch.Tensor, z: torch.Tensor, rays_d: torch.Tensor, B: float, noise: Optional[torch.Tensor],
-                  g_rgb: torch.Tensor, g_acc: torch.Tensor) -> torch.Tensor:
+                  g_rgb: torch.Tensor, g_acc: torch.Tensor, density_type: str = "relu", softplus_shift: float = 0.0) -> torch.Tensor:
     R, S = z.shape
+    a_type, a_shift = ops._act_args((density_type, softplus_shift))
     raw, z, rays_d = (ops._f32(t, n) for t, n in ((raw, "raw"), (z, "z"), (rays_d, "rays_d")))
     d_raw = torch.empty(R, S, 4, dtype=torch.float32, device=raw.device)
+    if a_type != 0:
+        _hip.check(_hip.lib().danbo_composite_bwd_lazy_act(_p(raw), None, None, _p(z), _p(rays_d), R, S, float(B),
+                                                           _p(ops._f32(noise, "noise")), _p(ops._f32(g_rgb, "g_rgb")),
+                                                           _p(ops._f32(g_acc, "g_acc")), _p(d_raw), a_type, a_shift, ops._stream()),
+                   "danbo_composite_bwd_lazy_act")
+        return d_raw
     _hip.check(_hip.lib().danbo_composite_bwd(_p(raw), _p(z), _p(rays_d), R, S, float(B), _p(ops._f32(noise, "noise")),
                                               _p(ops._f32(g_rgb, "g_rgb")), _p(ops._f32(g_acc, "g_acc")), _p(d_raw), ops._stream()),
                "danbo_composite_bwd")
@@ -67,14 +76,14 @@ def composite_bwd(raw: torch.Tensor, z: torch.Tensor, rays_d: torch.Tensor, B: f
 
 
 @composite_bwd.register_fake
-def _(raw, z, rays_d, B, noise, g_rgb, g_acc):
+def _(raw, z, rays_d, B, noise, g_rgb, g_acc, density_type="relu", softplus_shift=0.0):
     return raw.new_empty(tuple(z.shape) + (4,), dtype=torch.float32)
 
 
 def _composite_setup(ctx, inputs, output):
-    raw, z, rays_d, B, noise = inputs
+    raw, z, rays_d, B, noise, density_type, softplus_shift = inputs
     ctx.save_for_backward(raw, z, rays_d, noise)
-    ctx.B = B
+    ctx.B, ctx.density_type, ctx.softplus_shift = B, density_type, softplus_shift
 
 
 def _composite_backward(ctx, g_rgb, g_disp, g_acc, g_w, g_alpha):
@@ -83,8 +92,8 @@ def _composite_backward(ctx, g_rgb, g_disp, g_acc, g_w, g_alpha):
     R = z.shape[0]
     g_rgb = g_rgb if g_rgb is not None else raw.new_zeros(R, 3)
     g_acc = g_acc if g_acc is not None else raw.new_zeros(R)
-    return torch.ops.danbo.composite_bwd(raw, z, rays_d, ctx.B, noise, g_rgb.contiguous(), g_acc.contiguous()).reshape(raw.shape), \
-        None, None, None, None
+    return torch.ops.danbo.composite_bwd(raw, z, rays_d, ctx.B, noise, g_rgb.contiguous(), g_acc.contiguous(), ctx.density_type,
+                                         ctx.softplus_shift).reshape(raw.shape), None, None, None, None, None, None
 
 
 composite.register_autograd(_composite_backward, setup_context=_composite_setup)

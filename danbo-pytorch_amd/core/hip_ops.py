@@ -317,9 +317,38 @@ def fill_raw(raw_empty, S):
     return raw
 
 
-def composite(raw, z, rays_d, B=1.0, noise=None, bits=None, raw_empty=None, flat=None):
+RELU = ("relu", 0.0)
+_ACT_TYPES = {"relu": 0, "softplus": 1}      # DANBO_DENSITY_RELU / DANBO_DENSITY_SOFTPLUS (include/danbo_hip.h)
+
+
+def density_act(fn):
+    """-> (kind, shift) of a density activation: None / F.relu / RELU -> relu; the callable of raycasters.get_density_fn
+    (attributes density_kind, softplus_shift) or a (kind, shift) pair as they are.  Anything else raises: the composite kernels
+    implement these two (reference core/raycasters.py:192-200)."""
+    if fn is None:
+        return RELU
+    if isinstance(fn, tuple) and len(fn) == 2 and fn[0] in _ACT_TYPES:
+        return (fn[0], float(fn[1]) if fn[0] == "softplus" else 0.0)
+    kind = getattr(fn, "density_kind", None)
+    if kind == "softplus":
+        return ("softplus", float(fn.softplus_shift))
+    if kind == "relu" or fn is torch.nn.functional.relu or fn is torch.relu or getattr(fn, "__name__", "") == "relu":
+        return RELU
+    raise NotImplementedError("density activation: only relu and softplus (raycasters.get_density_fn) are implemented in the "
+                              "composite kernels")
+
+
+def _act_args(act):
+    kind, shift = density_act(act)
+    return _ACT_TYPES[kind], float(shift)
+
+
+def composite(raw, z, rays_d, B=1.0, noise=None, bits=None, raw_empty=None, flat=None, act=None):
     """bits / raw_empty: un-filled raw (samples with in-volume word 0 take raw_empty[ray]: danbo_hip.h);
-    flat: flat_rays(want_weights=True)'s result -- only its listed rays are composited, into its buffers"""
+    flat: flat_rays(want_weights=True)'s result -- only its listed rays are composited, into its buffers;
+    act: the density activation (density_act; default relu).  Softplus has no rays of constants: flat must be None."""
+    a_type, a_shift = _act_args(act)
+    assert a_type == 0 or flat is None, "rays of constants (flat=) do not exist under softplus"
     raw, z, rays_d = _f32(raw, "raw"), _f32(z, "z"), _f32(rays_d, "rays_d")
     R, S = z.shape
     dev = raw.device
@@ -333,7 +362,10 @@ def composite(raw, z, rays_d, B=1.0, noise=None, bits=None, raw_empty=None, flat
         acc = torch.empty(R, device=dev, dtype=torch.float32)
         w = torch.empty(R, S, device=dev, dtype=torch.float32)
         al = torch.empty(R, S, device=dev, dtype=torch.float32)
-    if flat is not None or bits is not None:
+    if a_type != 0:
+        _call("danbo_composite_rays_fwd_act", _p(raw), _p(_f32(raw_empty, "raw_empty")), _p(bits), _p(z), _p(rays_d), R, S, float(B),
+              _p(_f32(noise, "noise")), _p(rgb), _p(disp), _p(acc), _p(w), _p(al), None, None, a_type, a_shift, _stream())
+    elif flat is not None or bits is not None:
         _call("danbo_composite_rays_fwd", _p(raw), _p(_f32(raw_empty, "raw_empty")), _p(bits), _p(z), _p(rays_d), R, S, float(B),
               _p(_f32(noise, "noise")), _p(rgb), _p(disp), _p(acc), _p(w), _p(al), _p(flat["ray_list"] if flat else None),
               _p(flat["ray_count"] if flat else None), _stream())
@@ -399,12 +431,15 @@ def flat_rays(t_lo, ray_flat, S, Sf, want_weights=False, rows_later=False, cnt=N
 
 
 def composite_importance(raw, z, rays_d, Sf, B=1.0, noise=None, u=None, bits=None, raw_empty=None, want_weights=True,
-                         flat=None, two_net=False):
+                         flat=None, two_net=False, act=None):
     """coarse composite + importance resampling in one launch (S, Sf <= 64) ->
     (out0 dict, z_sorted, z_fine, sorted_idx); bits/raw_empty: un-filled raw (see danbo_hip.h).
     flat: flat_rays()'s result -- only its listed rays are composited, into its buffers (the rows of the other rays are already
     there; their z_sorted / sorted_idx rows are never made).
-    two_net: resample with the two-network pdf (danbo_composite_importance_pdf_fwd)."""
+    two_net: resample with the two-network pdf (danbo_composite_importance_pdf_fwd).
+    act: the density activation (density_act; default relu); flat must be None under softplus."""
+    a_type, a_shift = _act_args(act)
+    assert a_type == 0 or flat is None, "rays of constants (flat=) do not exist under softplus"
     raw, z, rays_d = _f32(raw, "raw"), _f32(z, "z"), _f32(rays_d, "rays_d")
     R, S = z.shape
     dev = raw.device
@@ -421,6 +456,11 @@ def composite_importance(raw, z, rays_d, Sf, B=1.0, noise=None, u=None, bits=Non
         zf = torch.empty(R, Sf, device=dev, dtype=torch.float32)
     zs = torch.empty(R, S + Sf, device=dev, dtype=torch.float32)
     idx = torch.empty(R, S + Sf, device=dev, dtype=torch.int32)
+    if a_type != 0:
+        _call("danbo_composite_importance_pdf_fwd_act", _p(raw), _p(_f32(raw_empty, "raw_empty")), _p(bits), _p(z), _p(rays_d), R, S,
+              int(Sf), float(B), _p(_f32(noise, "noise")), _p(_f32(u, "u")), int(bool(two_net)), _p(rgb), _p(disp), _p(acc), _p(w),
+              _p(al), _p(zf), _p(zs), _p(idx), None, None, a_type, a_shift, _stream())
+        return dict(rgb_map=rgb, disp_map=disp, acc_map=acc, weights=w, alpha=al), zs, zf, idx
     # (pdf 0 runs exactly the kernels of danbo_composite_importance_fwd)
     _call("danbo_composite_importance_pdf_fwd", _p(raw), _p(_f32(raw_empty, "raw_empty")), _p(bits), _p(z), _p(rays_d), R, S,
           int(Sf), float(B), _p(_f32(noise, "noise")), _p(_f32(u, "u")), int(bool(two_net)), _p(rgb), _p(disp), _p(acc), _p(w), _p(al),
@@ -429,9 +469,11 @@ def composite_importance(raw, z, rays_d, Sf, B=1.0, noise=None, u=None, bits=Non
 
 
 def composite_merged(raw_a, raw_b, idx, z_sorted, rays_d, B=1.0, noise=None, bits_a=None, bits_b=None, raw_empty=None,
-                     want_raw=False, flat=None):
+                     want_raw=False, flat=None, act=None):
     """final composite reading the coarse / importance raw through the sorted order (no merged copy);
-    flat: flat_rays()'s result, as composite_importance"""
+    flat: flat_rays()'s result, as composite_importance; act: the density activation, as composite"""
+    a_type, a_shift = _act_args(act)
+    assert a_type == 0 or flat is None, "rays of constants (flat=) do not exist under softplus"
     raw_a, raw_b, rays_d = _f32(raw_a, "raw_a"), _f32(raw_b, "raw_b"), _f32(rays_d, "rays_d")
     R, S = raw_a.shape[:2]
     Sf = raw_b.shape[1]
@@ -448,10 +490,15 @@ def composite_merged(raw_a, raw_b, idx, z_sorted, rays_d, B=1.0, noise=None, bit
         w = torch.empty(R, S + Sf, device=dev, dtype=torch.float32)
         al = torch.empty(R, S + Sf, device=dev, dtype=torch.float32)
     rs = torch.empty(R, S + Sf, 4, device=dev, dtype=torch.float32) if want_raw else None
-    _call("danbo_composite_merged_fwd", _p(raw_a), _p(raw_b), _p(_f32(raw_empty, "raw_empty")), _p(bits_a), _p(bits_b),
-          _p(idx), _p(_f32(z_sorted, "z_sorted")), _p(rays_d), R, S, Sf, float(B), _p(_f32(noise, "noise")), _p(rgb),
-          _p(disp), _p(acc), _p(w), _p(al), _p(rs), _p(flat["ray_list"] if flat else None),
-          _p(flat["ray_count"] if flat else None), _stream())
+    if a_type != 0:
+        _call("danbo_composite_merged_fwd_act", _p(raw_a), _p(raw_b), _p(_f32(raw_empty, "raw_empty")), _p(bits_a), _p(bits_b),
+              _p(idx), _p(_f32(z_sorted, "z_sorted")), _p(rays_d), R, S, Sf, float(B), _p(_f32(noise, "noise")), _p(rgb),
+              _p(disp), _p(acc), _p(w), _p(al), _p(rs), None, None, a_type, a_shift, _stream())
+    else:
+        _call("danbo_composite_merged_fwd", _p(raw_a), _p(raw_b), _p(_f32(raw_empty, "raw_empty")), _p(bits_a), _p(bits_b),
+              _p(idx), _p(_f32(z_sorted, "z_sorted")), _p(rays_d), R, S, Sf, float(B), _p(_f32(noise, "noise")), _p(rgb),
+              _p(disp), _p(acc), _p(w), _p(al), _p(rs), _p(flat["ray_list"] if flat else None),
+              _p(flat["ray_count"] if flat else None), _stream())
     out = dict(rgb_map=rgb, disp_map=disp, acc_map=acc, weights=w, alpha=al)
     if want_raw:
         out["raw_sorted"] = rs

@@ -61,8 +61,7 @@ class NeRF(nn.Module):
     # ---- compositing (reference :281-347) ----
     def raw2outputs(self, raw, z_vals, rays_d, raw_noise_std=0, pytest=False, B=0.01, rgb_act=torch.sigmoid,
                     act_fn=F.relu, rgb_eps=0.001, alpha_w=None, render_confd=False, render_entropy=False, **kwargs):
-        if act_fn is not F.relu and getattr(act_fn, "__name__", "") != "relu":
-            raise NotImplementedError("only density_type=relu is implemented in danbo_composite_fwd")
+        act = ops.density_act(act_fn)      # relu, or get_density_fn's softplus; any other callable raises NotImplementedError
         if alpha_w is not None or rgb_act is not torch.sigmoid:
             raise NotImplementedError("alpha_w / a colour activation other than sigmoid are out of scope")
         noise = None
@@ -82,8 +81,8 @@ class NeRF(nn.Module):
             raw = raw[..., :4]
         if raw.requires_grad:
             from .. import train_path
-            return train_path.composite(raw, z_vals, rays_d, B, noise)
-        return ops.composite(raw, z_vals, rays_d.reshape(-1, 3), B, noise)
+            return train_path.composite(raw, z_vals, rays_d, B, noise, act)
+        return ops.composite(raw, z_vals, rays_d.reshape(-1, 3), B, noise, act=act)
 
     def update_embed_fns(self, global_step, args):
         for fn in (self.pe_fn, self.dirs_pe_fn, self.bones_pe_fn):

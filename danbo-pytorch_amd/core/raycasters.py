@@ -22,10 +22,27 @@ from .networks import create_nerf
 from .utils.skeleton_utils import SMPLSkeleton, bone_align_transforms, get_skel_profile_from_rest_pose
 
 
+class SoftplusDensity:
+    """density = F.softplus(x - shift, beta=1), the reference's softplus lambda (raycasters.py:195-198) as a callable that also
+    tells the composite kernels what it is (hip_ops.density_act reads density_kind / softplus_shift)."""
+    density_kind = 'softplus'
+
+    def __init__(self, shift):
+        self.softplus_shift = float(shift)
+
+    def __call__(self, x):
+        return F.softplus(x - self.softplus_shift, beta=1)
+
+    def __repr__(self):
+        return f'SoftplusDensity(shift={self.softplus_shift})'
+
+
 def get_density_fn(args):
     if args.density_type == 'relu':
         return F.relu
-    raise NotImplementedError(f'density activation {args.density_type}: only relu is implemented')
+    if args.density_type == 'softplus':
+        return SoftplusDensity(getattr(args, 'softplus_shift', 1.0))
+    raise NotImplementedError(f'density activation {args.density_type} is undefined')
 
 
 def get_grad_vars(args, ray_caster):
@@ -218,12 +235,13 @@ class RayCaster(nn.Module):
         return eng
 
     def _engines(self, preproc_kwargs):
-        """-> (coarse engine, fine engine or None), both at the caller's density scale"""
+        """-> (coarse engine, fine engine or None), both at the caller's density scale and density activation"""
         eng = self._engine()
         eng.cfg['density_scale'] = preproc_kwargs.get('density_scale', eng.cfg['density_scale'])
+        eng.cfg['density_act'] = ops.density_act(preproc_kwargs.get('density_fn'))
         fine = self._engine(network=self.network_fine) if self.two_net else None
         if fine is not None:
-            fine.cfg['density_scale'] = eng.cfg['density_scale']
+            fine.cfg['density_scale'], fine.cfg['density_act'] = eng.cfg['density_scale'], eng.cfg['density_act']
         return eng, fine
 
     @staticmethod
@@ -266,7 +284,7 @@ class RayCaster(nn.Module):
         # ~25 kernels of the chain are captured once per chunk shape as a HIP graph and replayed.
         if self.use_graphs and R <= self.graph_max_rays and isinstance(eng, DanboEngine):
             key = (R, G, int(N_samples), int(N_importance), cams is not None, eng.cfg['use_volume_near_far'],
-                   float(eng.cfg['density_scale']))
+                   float(eng.cfg['density_scale']), tuple(eng.cfg['density_act']))
             return self._graphs.run([eng] if fine is None else [eng, fine], key, chain, ray_batch, skts_g, bones_g, cyls_g, cams)
         return chain(ray_batch, skts_g, bones_g, cyls_g, cams)
 
@@ -331,6 +349,7 @@ class RayCaster(nn.Module):
         rays_o, rays_d = ray_batch[:, 0:3].contiguous(), ray_batch[:, 3:6].contiguous()
         skts_g, bones_g, cyls_g = self._per_pose(skts, G), self._per_pose(bones, G), self._per_pose(cyls, G)
         B = preproc_kwargs.get('density_scale', 1.0)
+        act_fn = preproc_kwargs.get('density_fn', F.relu)     # (reference :334-337, :373-375: raw2outputs' act_fn)
         with torch.no_grad():
             near, far = ops.near_far_cylinder(rays_o, rays_d, cyls_g, 0., 1., R, ray_batch[:, 6], ray_batch[:, 7])
             if eng.cfg.get('use_volume_near_far'):
@@ -352,7 +371,7 @@ class RayCaster(nn.Module):
             return network(inputs)
 
         raw, enc = net(z, self.network)
-        out0 = self.network.raw2outputs(raw, z, rays_d, raw_noise_std=raw_noise_std, B=B)
+        out0 = self.network.raw2outputs(raw, z, rays_d, raw_noise_std=raw_noise_std, B=B, act_fn=act_fn)
         with torch.no_grad():
             u = torch.rand(R, N_importance, device=rays_o.device) if perturb > 0. else None
             if self.two_net:
@@ -361,7 +380,7 @@ class RayCaster(nn.Module):
                 z_all, z_fine, order = ops.importance_samples(z, out0['weights'], N_importance, u)
         if self.two_net:
             raw_f, enc_f = net(z_all, self.network_fine)
-            out = self.network_fine.raw2outputs(raw_f, z_all, rays_d, raw_noise_std=raw_noise_std, B=B)
+            out = self.network_fine.raw2outputs(raw_f, z_all, rays_d, raw_noise_std=raw_noise_std, B=B, act_fn=act_fn)
             ret = dict(rgb_map=out['rgb_map'], disp_map=out['disp_map'], acc_map=out['acc_map'], alpha=out['alpha'],
                        T_i=out['weights'], rgb0=out0['rgb_map'], disp0=out0['disp_map'], acc0=out0['acc_map'],
                        alpha0=out0['alpha'])
@@ -374,7 +393,7 @@ class RayCaster(nn.Module):
         idx = order.long().clamp_(0, N_samples + N_importance - 1)   # a permutation unless depths are NaN
         take = lambda a, b: torch.gather(torch.cat([a, b], 1), 1, idx[..., None].expand(-1, -1, a.shape[-1]))  # noqa: E731
         raw_all = take(raw, raw_f)
-        out = self.network.raw2outputs(raw_all, z_all, rays_d, raw_noise_std=raw_noise_std, B=B)
+        out = self.network.raw2outputs(raw_all, z_all, rays_d, raw_noise_std=raw_noise_std, B=B, act_fn=act_fn)
         ret = dict(rgb_map=out['rgb_map'], disp_map=out['disp_map'], acc_map=out['acc_map'], alpha=out['alpha'],
                    T_i=out['weights'], rgb0=out0['rgb_map'], disp0=out0['disp_map'], acc0=out0['acc_map'],
                    alpha0=out0['alpha'])

@@ -249,7 +249,8 @@ class DanboEngine:
     # ------------------------------------------------------------------ the same chain behind ONE C call
     def render_frame_c(self, rays_o, rays_d, skts, bones, cyls, cam_idx=None, N_samples=None, N_importance=None, chunk=4096):
         """`render()` through `danbo_render_frame` (include/danbo_hip.h): the library enqueues the whole chain itself, out of
-        one workspace buffer -- the entry point a C host binds.  Same kernels, same order: bit-identical outputs."""
+        one workspace buffer -- the entry point a C host binds.  Same kernels, same order: bit-identical outputs.  Under softplus
+        (cfg["density_act"]) through `danbo_render_frame_act`, which evaluates every ray whatever flat_rays_ok says."""
         import ctypes
         from . import _hip
         assert self.mlp_mode == "f16split" and self.mlp_form == 32
@@ -289,8 +290,13 @@ class DanboEngine:
         o = _hip.DanboFrameOut(**{k: v.data_ptr() for k, v in out.items()})
         nbytes = _hip.lib().danbo_render_frame_workspace(R, G, S, Sf, int(chunk), m.graph_width)
         ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-        _hip.check(_hip.lib().danbo_render_frame(ctypes.byref(m), ctypes.byref(r), S, Sf, ctypes.byref(o), ptr(ws), nbytes,
-                                                 ops._stream()), "danbo_render_frame")
+        a_type, a_shift = ops._act_args(cfg.get("density_act"))
+        if a_type != 0:
+            _hip.check(_hip.lib().danbo_render_frame_act(ctypes.byref(m), ctypes.byref(r), S, Sf, ctypes.byref(o), ptr(ws), nbytes,
+                                                         a_type, a_shift, ops._stream()), "danbo_render_frame_act")
+        else:
+            _hip.check(_hip.lib().danbo_render_frame(ctypes.byref(m), ctypes.byref(r), S, Sf, ctypes.byref(o), ptr(ws), nbytes,
+                                                     ops._stream()), "danbo_render_frame")
         out["T_i"] = out.pop("weights")
         return out
 
@@ -308,6 +314,7 @@ class DanboEngine:
         S = N_samples or cfg["N_samples"]
         Sf = N_importance or cfg["N_importance"]
         B = cfg["density_scale"]
+        act = ops.density_act(cfg.get("density_act"))     # (RayCaster._engines sets it per call, as density_scale)
         self.refresh()
         fused = S <= 64 and Sf <= 64
         lazy = not dense and not keep      # skip the raw pre-fill: consumers read raw_empty where bits == 0
@@ -318,7 +325,10 @@ class DanboEngine:
         # the flags allow, so they need no confirmation by the cull.
         # Longer rays (S > 64, up to 256 with Sf <= 64: the unfused composites) take the same constants: the coarse composite,
         # the resampling and the final composite walk the list there too.
-        flat_mode = lazy and (fused or (S <= 256 and Sf <= 64)) and self.skip_flat_rays and self.flat_rays_ok
+        # Relu only: softplus is positive everywhere, so a ray that misses every volume still has density on every sample (and,
+        # its last interval being 1e10, usually acc = 1) -- no ray is a ray of constants, whatever _flat_rays_ok() says.
+        flat_mode = (lazy and (fused or (S <= 256 and Sf <= 64)) and self.skip_flat_rays and self.flat_rays_ok
+                     and act[0] == "relu")
         near, far = self.near_far(rays_o, rays_d, cyls, skts, 0.0, 1.0, chunk) if near_far is None else near_far
         z = ops.coarse_samples(near, far, S)
         # candidate bones of every ray over [near, far] (coarse and importance depths both lie inside): the two culls skip the
@@ -340,17 +350,17 @@ class DanboEngine:
         if fused:
             out0, z_all, z_fine, order = ops.composite_importance(
                 raw, z, rays_d, Sf, B, bits=ex["valid_bits"] if lazy else None, raw_empty=view[1] if lazy else None,
-                want_weights=keep, flat=flat)
+                want_weights=keep, flat=flat, act=act)
         else:
             out0 = ops.composite(raw, z, rays_d, B, bits=ex["valid_bits"] if lazy else None, raw_empty=view[1] if lazy else None,
-                                 flat=flat)
+                                 flat=flat, act=act)
             z_all, z_fine, order = ops.importance_samples(z, out0["weights"], Sf, flat=flat)
         raw_f, ex_f = self.forward_samples(rays_o, rays_d, skts, bones, cam_idx, z=z_fine, dense=dense,
                                            volumes=vols, view=view, fill=not lazy,
                                            ray_mask=ray_mask, count=counts[1:2])
         out = ops.composite_merged(raw, raw_f, order, z_all, rays_d, B, bits_a=ex["valid_bits"] if lazy else None,
                                    bits_b=ex_f["valid_bits"] if lazy else None, raw_empty=view[1] if lazy else None,
-                                   want_raw=keep, flat=flat)
+                                   want_raw=keep, flat=flat, act=act)
         raw_all = out.get("raw_sorted")
         ret = dict(rgb_map=out["rgb_map"], disp_map=out["disp_map"], acc_map=out["acc_map"], alpha=out["alpha"],
                    T_i=out["weights"], rgb0=out0["rgb_map"], disp0=out0["disp_map"], acc0=out0["acc_map"],
@@ -377,6 +387,7 @@ class DanboEngine:
         S = N_samples or cfg["N_samples"]
         Sf = N_importance or cfg["N_importance"]
         B = cfg["density_scale"]
+        act = ops.density_act(cfg.get("density_act"))
         self.refresh()
         fine.refresh()
         lazy = not dense and not keep
@@ -391,15 +402,15 @@ class DanboEngine:
         bits, empty = (ex["valid_bits"], view[1]) if lazy else (None, None)
         if S <= 64 and Sf <= 64:
             out0, z_all, z_fine, order = ops.composite_importance(raw, z, rays_d, Sf, B, bits=bits, raw_empty=empty,
-                                                                  want_weights=keep, two_net=True)
+                                                                  want_weights=keep, two_net=True, act=act)
         else:
-            out0 = ops.composite(raw, z, rays_d, B, bits=bits, raw_empty=empty)
+            out0 = ops.composite(raw, z, rays_d, B, bits=bits, raw_empty=empty, act=act)
             z_all, z_fine, order = ops.importance_samples(z, out0["weights"], Sf, two_net=True)
         view_f = fine.view_constants(rays_d, skts, cam_idx)
         raw_f, ex_f = fine.forward_samples(rays_o, rays_d, skts, bones, cam_idx, z=z_all, dense=dense, volumes=fine.volumes(bones),
                                            view=view_f, fill=not lazy, ray_mask=masks[1], count=counts[1:2])
         bits_f, empty_f = (ex_f["valid_bits"], view_f[1]) if lazy else (None, None)
-        out = ops.composite(raw_f, z_all, rays_d, B, bits=bits_f, raw_empty=empty_f)
+        out = ops.composite(raw_f, z_all, rays_d, B, bits=bits_f, raw_empty=empty_f, act=act)
         ret = dict(rgb_map=out["rgb_map"], disp_map=out["disp_map"], acc_map=out["acc_map"], alpha=out["alpha"],
                    T_i=out["weights"], rgb0=out0["rgb_map"], disp0=out0["disp_map"], acc0=out0["acc_map"],
                    alpha0=out0["alpha"])

@@ -225,10 +225,12 @@ class AnerfColorFn(torch.autograd.Function):
         return d_featv / sig, (d_alpha4[:, 0] / sig).reshape(n, 1), dC, d_pre_ray, g_rgb_w, g_rgb_b, None, None, None
 
 
-def composite(raw, z, rays_d, B=1.0, noise=None):
-    """NeRF.raw2outputs with gradients for rgb_map and acc_map (K4): torch.ops.danbo.composite (core/custom_ops.py)"""
+def composite(raw, z, rays_d, B=1.0, noise=None, act=None):
+    """NeRF.raw2outputs with gradients for rgb_map and acc_map (K4): torch.ops.danbo.composite (core/custom_ops.py);
+    act: the density activation (hip_ops.density_act; default relu)"""
+    kind, shift = ops.density_act(act)
     rgb, disp, acc, w, al = torch.ops.danbo.composite(raw.contiguous().float(), z.contiguous().float(),
-                                                      rays_d.reshape(-1, 3).contiguous().float(), float(B), noise)
+                                                      rays_d.reshape(-1, 3).contiguous().float(), float(B), noise, kind, float(shift))
     return dict(rgb_map=rgb, disp_map=disp, acc_map=acc, weights=w, alpha=al)
 
 

@@ -8,6 +8,9 @@
 #include "sample_math.hpp"
 
 #define DANBO_CHECK_ARG(cond) do { if (!(cond)) return DANBO_EINVAL; } while (0)
+// the density activation of an `_act` entry point (danbo_hip.h): a known type and a finite shift, before any launch
+#define DANBO_CHECK_DENSITY_ACT(act, shift) \
+    DANBO_CHECK_ARG(((act) == DANBO_DENSITY_RELU || (act) == DANBO_DENSITY_SOFTPLUS) && (shift) - (shift) == 0.f)
 #define DANBO_LAUNCH_RET() do { hipError_t e_ = hipGetLastError(); return e_ == hipSuccess ? 0 : (int)e_; } while (0)
 
 // Opt a kernel into more than 64 KB of dynamic LDS.  The attribute is per DEVICE: the "done" mask is keyed by the calling

@@ -100,10 +100,12 @@ __global__ __launch_bounds__(GB_BLOCK) void k_bone_gather_bwd(const float* __res
 //   w_i = a_i T_i, T_i = prod_{k<i} (1 - a_k + 1e-10), rgb_map = sum w_i c_i, acc = min(sum w_i, 1)
 //   dL/dw_i = <g_rgb, c_i> + g_acc [sum w < 1]
 //   dL/da_i = dL/dw_i T_i - (sum_{k>i} dL/dw_k w_k) / (1 - a_i + 1e-10)
-//   a_i = 1 - exp(-s_i delta_i), s_i = relu(raw3_i / B + noise_i)
+//   a_i = 1 - exp(-s_i delta_i), s_i = act(raw3_i / B + noise_i): relu or softplus(. - shift) (DA; shift sits in the padding
+//   between B and the next pointer, so no other kernel argument moves)
 // ======================================================================================
+template <int DA>
 __global__ __launch_bounds__(256) void k_composite_bwd(const float4* __restrict__ raw, const float* __restrict__ z,
-                                                       const float* __restrict__ rays_d, int R, int S, float B,
+                                                       const float* __restrict__ rays_d, int R, int S, float B, float shift,
                                                        const float* __restrict__ noise,
                                                        const float* __restrict__ g_rgb, const float* __restrict__ g_acc,
                                                        float4* __restrict__ d_raw, const float4* __restrict__ raw_empty,
@@ -112,8 +114,8 @@ __global__ __launch_bounds__(256) void k_composite_bwd(const float4* __restrict_
     const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int nwaves = (gridDim.x * blockDim.x) >> 6;
     for (int r = wave; r < R; r += nwaves)
-        composite_bwd_ray(raw, z, rays_d, r, S, B, noise, g_rgb[3 * r], g_rgb[3 * r + 1], g_rgb[3 * r + 2], g_acc[r], raw_empty, bits, lane,
-                          [&](int s, const float4& o) { d_raw[(size_t)r * S + s] = o; });
+        composite_bwd_ray<DA>(raw, z, rays_d, r, S, B, noise, g_rgb[3 * r], g_rgb[3 * r + 1], g_rgb[3 * r + 2], g_acc[r], raw_empty, bits, lane,
+                              [&](int s, const float4& o) { d_raw[(size_t)r * S + s] = o; }, shift);
 }
 
 }  // namespace danbo
@@ -134,15 +136,31 @@ extern "C" int danbo_bone_gather_bwd(const float* rays_o, const float* rays_d, c
     DANBO_LAUNCH_RET();
 }
 
+template <int DA>
+static int composite_bwd_impl(const float* raw, const float* raw_empty, const uint32_t* valid_bits, const float* z,
+                              const float* rays_d, int R, int S, float B, const float* noise, const float* g_rgb,
+                              const float* g_acc, float* d_raw, float shift, void* stream) {
+    DANBO_CHECK_ARG(R > 0 && S > 0 && S <= 256 && B > 0.f && raw && z && rays_d && g_rgb && g_acc && d_raw);
+    DANBO_CHECK_ARG(valid_bits == nullptr || raw_empty != nullptr);
+    hipLaunchKernelGGL(k_composite_bwd<DA>, dim3(stream_grid((long)R * 64, 256)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const float4*>(raw), z, rays_d, R, S, B, shift, noise, g_rgb, g_acc,
+                       reinterpret_cast<float4*>(d_raw), reinterpret_cast<const float4*>(raw_empty), valid_bits);
+    DANBO_LAUNCH_RET();
+}
+
 extern "C" int danbo_composite_bwd_lazy(const float* raw, const float* raw_empty, const uint32_t* valid_bits, const float* z,
                                          const float* rays_d, int R, int S, float B, const float* noise, const float* g_rgb,
                                          const float* g_acc, float* d_raw, void* stream) {
-    DANBO_CHECK_ARG(R > 0 && S > 0 && S <= 256 && B > 0.f && raw && z && rays_d && g_rgb && g_acc && d_raw);
-    DANBO_CHECK_ARG(valid_bits == nullptr || raw_empty != nullptr);
-    hipLaunchKernelGGL(k_composite_bwd, dim3(stream_grid((long)R * 64, 256)), dim3(256), 0, (hipStream_t)stream,
-                       reinterpret_cast<const float4*>(raw), z, rays_d, R, S, B, noise, g_rgb, g_acc,
-                       reinterpret_cast<float4*>(d_raw), reinterpret_cast<const float4*>(raw_empty), valid_bits);
-    DANBO_LAUNCH_RET();
+    return composite_bwd_impl<DENSITY_RELU>(raw, raw_empty, valid_bits, z, rays_d, R, S, B, noise, g_rgb, g_acc, d_raw, 0.f, stream);
+}
+
+extern "C" int danbo_composite_bwd_lazy_act(const float* raw, const float* raw_empty, const uint32_t* valid_bits, const float* z,
+                                             const float* rays_d, int R, int S, float B, const float* noise, const float* g_rgb,
+                                             const float* g_acc, float* d_raw, int act, float shift, void* stream) {
+    DANBO_CHECK_DENSITY_ACT(act, shift);
+    return act == DENSITY_SOFTPLUS
+               ? composite_bwd_impl<DENSITY_SOFTPLUS>(raw, raw_empty, valid_bits, z, rays_d, R, S, B, noise, g_rgb, g_acc, d_raw, shift, stream)
+               : composite_bwd_impl<DENSITY_RELU>(raw, raw_empty, valid_bits, z, rays_d, R, S, B, noise, g_rgb, g_acc, d_raw, 0.f, stream);
 }
 
 extern "C" int danbo_composite_bwd(const float* raw, const float* z, const float* rays_d, int R, int S, float B,

@@ -66,13 +66,16 @@ extern "C" size_t danbo_render_frame_workspace(int R, int G, int S, int Sf, int 
 
 #define DANBO_TRY(call) do { const int rc_ = (call); if (rc_ != 0) return rc_; } while (0)
 
-extern "C" int danbo_render_frame(const DanboModel* m, const DanboRays* r, int S, int Sf, const DanboFrameOut* o, void* workspace,
-                                  size_t workspace_bytes, void* stream) {
+// act / shift: the density activation of the three composites (danbo_hip.h).  Softplus: no rays of constants, whatever the
+// model says -- the density of empty space is positive on every sample, so every ray is evaluated
+static int render_frame_impl(const DanboModel* m, const DanboRays* r, int S, int Sf, const DanboFrameOut* o, void* workspace,
+                             size_t workspace_bytes, int act, float shift, void* stream) {
     DANBO_CHECK_ARG(m && r && o && workspace && S >= 3 && S <= 256 && Sf >= 1 && Sf <= 64);
     DANBO_CHECK_ARG(r->R >= 1 && r->G >= 1 && r->R % r->G == 0 && r->chunk >= 1);
     DANBO_CHECK_ARG(r->rays_o && r->rays_d && r->skts && r->bones && r->cyls);
     DANBO_CHECK_ARG(o->rgb_map && o->disp_map && o->acc_map && o->alpha && o->weights && o->rgb0 && o->disp0 && o->acc0 && o->alpha0);
     const int R = r->R, G = r->G;
+    const bool flat_rays = m->flat_rays_ok != 0 && act == DANBO_DENSITY_RELU;
     DANBO_CHECK_ARG(workspace_bytes >= danbo_render_frame_workspace(R, G, S, Sf, r->chunk, m->graph_width));
     Carver c{reinterpret_cast<char*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255), 0, workspace_bytes};
     const FrameBuffers b = carve(c, R, G, S, Sf, r->chunk, m->graph_width);
@@ -86,12 +89,11 @@ extern "C" int danbo_render_frame(const DanboModel* m, const DanboRays* r, int S
     DANBO_TRY(danbo_coarse_samples(b.near, b.far, R, S, nullptr, b.z, stream));
     // candidate bones of every ray over [near, far]: both culls below skip the rays (and workgroups) that miss every volume
     DANBO_TRY(danbo_ray_bone_mask(r->rays_o, r->rays_d, b.near, b.far, R, G, r->skts, m->align, m->axis_scale, b.ray_mask,
-                                  m->flat_rays_ok ? b.ray_flat : nullptr, stream));
+                                  flat_rays ? b.ray_flat : nullptr, stream));
     // per pose / per ray
     DANBO_TRY(danbo_pose_volumes_fwd(r->bones, G, m->L_graph, m->graph_width, m->g_w0, m->g_adjw0, m->g_b0, m->g_w1, m->g_adjw1, m->g_b1,
                                      m->g_w2, m->g_b2, m->g_w3, m->g_b3, b.vol_scratch, b.volumes, stream));
     zero_words(b.count, 4, nullptr, 0, st);      // both row counters, the ticket (which returns to 0 after each launch), the ray counter
-    const bool flat_rays = m->flat_rays_ok != 0;
     auto view_consts = [&](const int32_t* ray_list, const int32_t* ray_count) -> int {
         return danbo_view_consts(r->rays_d, r->skts, R, G, m->ray_mode, m->normalise, m->L_view, m->framecodes, m->n_codes, m->code_size,
                                  m->mean_code, r->cam_idx, m->views_w_ray_t, m->views_b_eff, m->rgb_w, m->rgb_b, m->empty_consts, 2,
@@ -126,18 +128,29 @@ extern "C" int danbo_render_frame(const DanboModel* m, const DanboRays* r, int S
     DANBO_TRY(cull(b.z, S, b.bits_a, b.count));
     DANBO_TRY(network(b.z, S, b.bits_a, b.count, b.raw_a));
     if (S <= 64) {
-        DANBO_TRY(danbo_composite_importance_fwd(b.raw_a, b.raw_empty, b.bits_a, b.z, r->rays_d, R, S, Sf, m->density_scale, nullptr,
-                                                 nullptr, o->rgb0, o->disp0, o->acc0, nullptr, o->alpha0, b.z_fine, b.z_sorted, b.order,
-                                                 ray_list, ray_count, stream));
+        DANBO_TRY(danbo_composite_importance_pdf_fwd_act(b.raw_a, b.raw_empty, b.bits_a, b.z, r->rays_d, R, S, Sf, m->density_scale, nullptr,
+                                                         nullptr, 0, o->rgb0, o->disp0, o->acc0, nullptr, o->alpha0, b.z_fine, b.z_sorted,
+                                                         b.order, ray_list, ray_count, act, shift, stream));
     } else {     // rays of more than 64 coarse samples: the same two steps as two launches, the weights in between
-        DANBO_TRY(danbo_composite_rays_fwd(b.raw_a, b.raw_empty, b.bits_a, b.z, r->rays_d, R, S, m->density_scale, nullptr, o->rgb0,
-                                           o->disp0, o->acc0, b.weights0, o->alpha0, ray_list, ray_count, stream));
+        DANBO_TRY(danbo_composite_rays_fwd_act(b.raw_a, b.raw_empty, b.bits_a, b.z, r->rays_d, R, S, m->density_scale, nullptr, o->rgb0,
+                                               o->disp0, o->acc0, b.weights0, o->alpha0, ray_list, ray_count, act, shift, stream));
         DANBO_TRY(danbo_importance_samples_rays(b.z, b.weights0, R, S, Sf, nullptr, b.z_fine, b.z_sorted, b.order, ray_list, ray_count,
                                                 stream));
     }
     DANBO_TRY(cull(b.z_fine, Sf, b.bits_b, b.count + 1));
     DANBO_TRY(network(b.z_fine, Sf, b.bits_b, b.count + 1, b.raw_b));
-    return danbo_composite_merged_fwd(b.raw_a, b.raw_b, b.raw_empty, b.bits_a, b.bits_b, b.order, b.z_sorted, r->rays_d, R, S, Sf,
-                                      m->density_scale, nullptr, o->rgb_map, o->disp_map, o->acc_map, o->weights, o->alpha, nullptr,
-                                      ray_list, ray_count, stream);
+    return danbo_composite_merged_fwd_act(b.raw_a, b.raw_b, b.raw_empty, b.bits_a, b.bits_b, b.order, b.z_sorted, r->rays_d, R, S, Sf,
+                                          m->density_scale, nullptr, o->rgb_map, o->disp_map, o->acc_map, o->weights, o->alpha, nullptr,
+                                          ray_list, ray_count, act, shift, stream);
+}
+
+extern "C" int danbo_render_frame(const DanboModel* m, const DanboRays* r, int S, int Sf, const DanboFrameOut* o, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    return render_frame_impl(m, r, S, Sf, o, workspace, workspace_bytes, DANBO_DENSITY_RELU, 0.f, stream);
+}
+
+extern "C" int danbo_render_frame_act(const DanboModel* m, const DanboRays* r, int S, int Sf, const DanboFrameOut* o, void* workspace,
+                                      size_t workspace_bytes, int act, float shift, void* stream) {
+    DANBO_CHECK_DENSITY_ACT(act, shift);
+    return render_frame_impl(m, r, S, Sf, o, workspace, workspace_bytes, act, act == DANBO_DENSITY_SOFTPLUS ? shift : 0.f, stream);
 }

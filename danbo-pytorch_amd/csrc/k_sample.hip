@@ -747,12 +747,14 @@ __device__ __forceinline__ int scattered_ray(long g, unsigned scatter, int R) {
 
 // one 64-sample chunk of a ray: rw = raw of this lane's sample, zs its depth, gap = z[s+1] - z[s] (1e10 for the
 // last sample of the ray), nz = optional density noise.  Returns the sample's weight; al = its alpha.
+// DA / shift: the density activation (density_act, sample_math.hpp); the relu form never reads the shift.
+template <int DA>
 __device__ __forceinline__ float composite_chunk(CompositeState& st, const float4 rw, float zs, float gap, float dn,
-                                                 float B, bool has_noise, float nz, bool act, int lane, float& al) {
+                                                 float B, bool has_noise, float nz, bool act, int lane, float& al, float shift) {
     const float dist = mul_rn(gap, dn);
     float sig = div_rn(rw.w, B);
     if (has_noise) sig = add_rn(sig, nz);
-    sig = fmaxf(sig, 0.f);
+    sig = density_act<DA>(sig, shift);
     al = sub_rn(1.0f, expf(-mul_rn(sig, dist)));
     if (!act) al = 0.f;
     const float t = act ? add_rn(sub_rn(1.0f, al), 1e-10f) : 1.0f;
@@ -791,9 +793,11 @@ __device__ __forceinline__ float ray_norm(const float* __restrict__ rays_d, int 
 
 // raw_empty / bits (optional, together): samples whose in-volume word is 0 were never written by K3 and take the ray's
 // empty-space raw (the convention of the fused composites); ray_list / ray_count (optional): only the listed rays
+// (shift sits in the padding between B and the next pointer: no other kernel argument moves)
+template <int DA>
 __global__ __launch_bounds__(256) void k_composite(const float4* __restrict__ raw, const float4* __restrict__ raw_empty,
                                                    const uint32_t* __restrict__ bits, const float* __restrict__ z,
-                                                   const float* __restrict__ rays_d, int R, int S, float B,
+                                                   const float* __restrict__ rays_d, int R, int S, float B, float shift,
                                                    const float* __restrict__ noise, float* __restrict__ rgb_map,
                                                    float* __restrict__ disp, float* __restrict__ acc_out,
                                                    float* __restrict__ weights, float* __restrict__ alpha_out,
@@ -816,7 +820,7 @@ __global__ __launch_bounds__(256) void k_composite(const float4* __restrict__ ra
             float4 rw = re;
             if (bits == nullptr || bits[m] != 0u) rw = raw[m];
             float al;
-            const float w = composite_chunk(st, rw, zs, gap, dn, B, noise != nullptr, noise ? noise[m] : 0.f, act, lane, al);
+            const float w = composite_chunk<DA>(st, rw, zs, gap, dn, B, noise != nullptr, noise ? noise[m] : 0.f, act, lane, al, shift);
             if (act) {
                 if (weights) weights[m] = w;
                 if (alpha_out) alpha_out[m] = al;
@@ -833,113 +837,26 @@ __global__ __launch_bounds__(256) void k_composite(const float4* __restrict__ ra
 // (amdgpu_waves_per_eu(8, 8): the compiler's 103 - 106 SGPRs allowed seven wavefronts per SIMD; a ray is a chain of dependent memory
 // round trips that only other wavefronts cover -- with 78 SGPRs and eight: 201 -> 164 us over a whole frame, 303 -> 277 for
 // k_composite_importance, the frame -0.4 %)
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_composite_merged(const float4* __restrict__ raw_a, const float4* __restrict__ raw_b,
-                                                          const float4* __restrict__ raw_empty,
-                                                          const uint32_t* __restrict__ bits_a,
-                                                          const uint32_t* __restrict__ bits_b,
-                                                          const int32_t* __restrict__ sorted_idx,
-                                                          const float* __restrict__ z, const float* __restrict__ rays_d,
-                                                          int R, int S, int Sf, float B, const float* __restrict__ noise,
-                                                          float* __restrict__ rgb_map, float* __restrict__ disp,
-                                                          float* __restrict__ acc_out, float* __restrict__ weights,
-                                                          float* __restrict__ alpha_out, float4* __restrict__ raw_sorted,
-                                                          const int32_t* __restrict__ ray_list,
-                                                          const int32_t* __restrict__ ray_count, unsigned scatter) {
-    const int lane = threadIdx.x & 63;
-    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int nwaves = (gridDim.x * blockDim.x) >> 6;
-    const int St = S + Sf;
-    if (St <= 64) {
-        // one chunk per ray, software-pipelined over the wavefront's rays: a ray is the chain sorted_idx -> in-volume word -> raw;
-        // the index of ray r + 2 and the word of ray r + 1 are in flight while ray r is composited
-        const bool act = lane < St;
-        struct Idx { int src; float zs, z1, dn; float4 re; };
-        auto fetch_idx = [&](int r) {
-            Idx in;
-            const size_t m = (size_t)r * St + (act ? lane : St - 1);
-            in.src = min(max(sorted_idx[m], 0), St - 1);     // NaN depths must not become an out-of-bounds read
-            in.zs = z[m];
-            in.z1 = (lane + 1 < St) ? z[m + 1] : 0.f;
-            in.dn = ray_norm(rays_d, r);
-            in.re = raw_empty ? raw_empty[r] : float4{0.f, 0.f, 0.f, 0.f};
-            return in;
-        };
-        auto fetch_word = [&](int r, int src) -> uint32_t {
-            if (src < S) return bits_a ? bits_a[(size_t)r * S + src] : 1u;
-            return bits_b ? bits_b[(size_t)r * Sf + (src - S)] : 1u;
-        };
-        // item i of the launch: the i-th listed ray, or (no list) ray scattered_ray(i); the index of item i + 2 and the word of
-        // item i + 1 are in flight while item i is composited
-        const int n = ray_list ? min(max(*ray_count, 0), R) : R;
-        auto ray_at = [&](int i) { return i < n ? (ray_list ? min(max(ray_list[i], 0), R - 1) : scattered_ray(i, scatter, R)) : -1; };
-        int r = ray_at(wave), r_nxt = ray_at(wave + nwaves);
-        if (r < 0) return;
-        Idx cur = fetch_idx(r), nxt = fetch_idx(r_nxt >= 0 ? r_nxt : r);
-        uint32_t cur_word = fetch_word(r, cur.src);
-        for (int i = wave; i < n; i += nwaves) {
-            CompositeState st = {1.0f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            const size_t m = (size_t)r * St + (act ? lane : St - 1);
-            float4 rw = cur.re;
-            if (cur_word != 0u) rw = cur.src < S ? raw_a[(size_t)r * S + cur.src] : raw_b[(size_t)r * Sf + (cur.src - S)];
-            const int r_n = r_nxt >= 0 ? r_nxt : r;
-            const uint32_t nxt_word = fetch_word(r_n, nxt.src);
-            const int r_nn = ray_at(i + 2 * nwaves);
-            const Idx nn = fetch_idx(r_nn >= 0 ? r_nn : r_n);
-            const float gap = (lane + 1 < St) ? sub_rn(cur.z1, cur.zs) : 1e10f;
-            float al, w;
-            // a ray without an in-volume sample in either pass: constants, as in k_composite_importance below (bit for bit)
-            const float dist = mul_rn(gap, cur.dn);
-            const float rgb_sum = add_rn(add_rn(cur.re.x, cur.re.y), cur.re.z);
-            const bool flat = raw_empty != nullptr && bits_a != nullptr && bits_b != nullptr && noise == nullptr &&
-                              !(div_rn(cur.re.w, B) > 0.f) && sub_rn(rgb_sum, rgb_sum) == 0.f &&
-                              __all(cur_word == 0u && sub_rn(dist, dist) == 0.f);
-            if (flat) {
-                al = 0.f;
-                w = 0.f;
-            } else {
-                w = composite_chunk(st, rw, cur.zs, gap, cur.dn, B, noise != nullptr, noise ? noise[m] : 0.f, act, lane, al);
-            }
-            if (act) {
-                if (weights) weights[m] = w;
-                if (alpha_out) alpha_out[m] = al;
-                if (raw_sorted) raw_sorted[m] = rw;
-            }
-            if (lane == 0) composite_finish(st, r, rgb_map, disp, acc_out);
-            cur = nxt; cur_word = nxt_word; nxt = nn; r = r_n; r_nxt = r_nn;
-        }
-        return;
-    }
-    const int n_all = ray_list ? min(max(*ray_count, 0), R) : R;
-    for (int i = wave; i < n_all; i += nwaves) {
-        const int r = ray_list ? min(max(ray_list[i], 0), R - 1) : i;
-        const float dn = ray_norm(rays_d, r);
-        CompositeState st = {1.0f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        for (int c0 = 0; c0 < St; c0 += 64) {
-            const int s = c0 + lane;
-            const bool act = s < St;
-            const size_t m = (size_t)r * St + (act ? s : St - 1);
-            const int src = min(max(sorted_idx[m], 0), St - 1);   // NaN depths must not become an out-of-bounds read
-            float4 rw;
-            if (src < S) {
-                const size_t q = (size_t)r * S + src;
-                rw = (bits_a && bits_a[q] == 0u) ? raw_empty[r] : raw_a[q];
-            } else {
-                const size_t q = (size_t)r * Sf + (src - S);
-                rw = (bits_b && bits_b[q] == 0u) ? raw_empty[r] : raw_b[q];
-            }
-            const float zs = z[m];
-            const float gap = (s + 1 < St) ? sub_rn(z[m + 1], zs) : 1e10f;
-            float al;
-            const float w = composite_chunk(st, rw, zs, gap, dn, B, noise != nullptr, noise ? noise[m] : 0.f, act, lane, al);
-            if (act) {
-                if (weights) weights[m] = w;
-                if (alpha_out) alpha_out[m] = al;
-                if (raw_sorted) raw_sorted[m] = rw;
-            }
-        }
-        if (lane == 0) composite_finish(st, r, rgb_map, disp, acc_out);
-    }
+// DA / shift: the density activation.  The body is composite_merged_body.inc, included into two plain kernels (see there why this
+// one is not a kernel template like its neighbours); the relu kernel keeps its name and its arguments.
+#define DANBO_MERGED_PARAMS                                                                                                      \
+    const float4 *__restrict__ raw_a, const float4 *__restrict__ raw_b, const float4 *__restrict__ raw_empty,                    \
+        const uint32_t *__restrict__ bits_a, const uint32_t *__restrict__ bits_b, const int32_t *__restrict__ sorted_idx,        \
+        const float *__restrict__ z, const float *__restrict__ rays_d, int R, int S, int Sf, float B,                            \
+        const float *__restrict__ noise, float *__restrict__ rgb_map, float *__restrict__ disp, float *__restrict__ acc_out,     \
+        float *__restrict__ weights, float *__restrict__ alpha_out, float4 *__restrict__ raw_sorted,                             \
+        const int32_t *__restrict__ ray_list, const int32_t *__restrict__ ray_count, unsigned scatter
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_composite_merged(DANBO_MERGED_PARAMS) {
+    constexpr int DA = DENSITY_RELU;
+    const float shift = 0.f;
+#include "composite_merged_body.inc"
 }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_composite_merged_softplus(DANBO_MERGED_PARAMS,
+                                                                                                              float shift) {
+    constexpr int DA = DENSITY_SOFTPLUS;
+#include "composite_merged_body.inc"
+}
+#undef DANBO_MERGED_PARAMS
 
 // ======================================================================================
 // importance sampling + merge
@@ -1214,7 +1131,8 @@ __global__ __launch_bounds__(256) void k_importance_wave_long(const float* __res
 // coarse composite + importance resampling of a ray in one pass (S, Sf <= 64): the weights never leave the
 // wavefront's registers unless the caller asks for them.  Item i of the launch is the i-th listed ray (ray_list / ray_count:
 // k_flat_rays' list of the rays that are NOT rays of constants) or, without a list, ray scattered_ray(i).
-template <bool DET, bool TWO = false>
+// DA / shift: the density activation (shift is the last argument, in the padding behind scatter).
+template <bool DET, bool TWO = false, int DA = DENSITY_RELU>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_composite_importance(const float4* __restrict__ raw,
                                                               const float4* __restrict__ raw_empty,
                                                               const uint32_t* __restrict__ bits,
@@ -1226,7 +1144,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
                                                               float* __restrict__ z_fine, float* __restrict__ z_sorted,
                                                               int32_t* __restrict__ sorted_idx,
                                                               const int32_t* __restrict__ ray_list,
-                                                              const int32_t* __restrict__ ray_count, unsigned scatter) {
+                                                              const int32_t* __restrict__ ray_count, unsigned scatter, float shift) {
     const int lane = threadIdx.x & 63;
     const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int nwaves = (gridDim.x * blockDim.x) >> 6;
@@ -1265,17 +1183,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         // pre-activation is <= 0 (or NaN: fmaxf drops it) and every interval length is finite, the general chain below computes
         // sig = 0, alpha = 1 - exp(-0) = +0, T = 1, w = +0 for every sample and +0 for all five sums: the maps are constants.
         // Taken wave-uniformly, bit for bit the general result (the importance depths still go through importance_wave: they
-        // depend on the ray's depths only).
-        const float dist = mul_rn(gap, cur.dn);
-        const float rgb_sum = add_rn(add_rn(cur.re.x, cur.re.y), cur.re.z);     // (NaN / inf colour logits would make 0 * c a NaN)
-        const bool flat = bits != nullptr && noise == nullptr && !(div_rn(cur.re.w, B) > 0.f) && sub_rn(rgb_sum, rgb_sum) == 0.f &&
-                          __all(cur.word == 0u && sub_rn(dist, dist) == 0.f);
+        // depend on the ray's depths only).  Relu only: under softplus the density of such a ray is positive on every sample, the
+        // condition can never hold and the path is compiled out.
+        bool flat = false;
+        if constexpr (DA == DENSITY_RELU) {
+            const float dist = mul_rn(gap, cur.dn);
+            const float rgb_sum = add_rn(add_rn(cur.re.x, cur.re.y), cur.re.z);     // (NaN / inf colour logits would make 0 * c a NaN)
+            flat = bits != nullptr && noise == nullptr && !(div_rn(cur.re.w, B) > 0.f) && sub_rn(rgb_sum, rgb_sum) == 0.f &&
+                   __all(cur.word == 0u && sub_rn(dist, dist) == 0.f);
+        }
         if (flat) {
             al = 0.f;
             w = 0.f;
             st.sr = st.sg = st.sb = st.sd = st.sa = 0.f;
         } else {
-            w = composite_chunk(st, rw, zs, gap, cur.dn, B, noise != nullptr, noise ? noise[m] : 0.f, act, lane, al);
+            w = composite_chunk<DA>(st, rw, zs, gap, cur.dn, B, noise != nullptr, noise ? noise[m] : 0.f, act, lane, al, shift);
         }
         if (act) {
             if (weights) weights[m] = w;
@@ -1479,29 +1401,42 @@ extern "C" int danbo_merge_samples(const float* a, const float* b, const int32_t
     DANBO_LAUNCH_RET();
 }
 
+template <int DA>
 static int composite_impl(const float* raw, const float* raw_empty, const uint32_t* bits, const float* z, const float* rays_d, int R,
                           int S, float B, const float* noise, float* rgb_map, float* disp, float* acc, float* weights, float* alpha,
-                          const int32_t* ray_list, const int32_t* ray_count, void* stream) {
+                          const int32_t* ray_list, const int32_t* ray_count, float shift, void* stream) {
     DANBO_CHECK_ARG(R > 0 && S > 0 && B > 0.f);
     DANBO_CHECK_ARG((ray_list == nullptr) == (ray_count == nullptr) && (bits == nullptr || raw_empty != nullptr));
-    static const int per_launch = resident_grid(k_composite, 1L << 40, 256);
+    static const int per_launch = resident_grid(k_composite<DA>, 1L << 40, 256);
     const int grid = (int)std::min<long>(ceil_div((long)R * 64, 256), per_launch);
-    hipLaunchKernelGGL(k_composite, dim3(grid), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float4*>(raw),
-                       reinterpret_cast<const float4*>(raw_empty), bits, z, rays_d, R, S, B, noise, rgb_map, disp, acc, weights, alpha,
-                       ray_list, ray_count);
+    hipLaunchKernelGGL(k_composite<DA>, dim3(grid), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float4*>(raw),
+                       reinterpret_cast<const float4*>(raw_empty), bits, z, rays_d, R, S, B, shift, noise, rgb_map, disp, acc, weights,
+                       alpha, ray_list, ray_count);
     DANBO_LAUNCH_RET();
 }
 extern "C" int danbo_composite_fwd(const float* raw, const float* z, const float* rays_d, int R, int S, float B,
                                     const float* noise, float* rgb_map, float* disp, float* acc, float* weights,
                                     float* alpha, void* stream) {
-    return composite_impl(raw, nullptr, nullptr, z, rays_d, R, S, B, noise, rgb_map, disp, acc, weights, alpha, nullptr, nullptr, stream);
+    return composite_impl<DENSITY_RELU>(raw, nullptr, nullptr, z, rays_d, R, S, B, noise, rgb_map, disp, acc, weights, alpha, nullptr,
+                                        nullptr, 0.f, stream);
 }
 extern "C" int danbo_composite_rays_fwd(const float* raw, const float* raw_empty, const uint32_t* valid_bits, const float* z,
                                          const float* rays_d, int R, int S, float B, const float* noise, float* rgb_map,
                                          float* disp, float* acc, float* weights, float* alpha, const int32_t* ray_list,
                                          const int32_t* ray_count, void* stream) {
-    return composite_impl(raw, raw_empty, valid_bits, z, rays_d, R, S, B, noise, rgb_map, disp, acc, weights, alpha, ray_list, ray_count,
-                          stream);
+    return composite_impl<DENSITY_RELU>(raw, raw_empty, valid_bits, z, rays_d, R, S, B, noise, rgb_map, disp, acc, weights, alpha, ray_list,
+                                        ray_count, 0.f, stream);
+}
+extern "C" int danbo_composite_rays_fwd_act(const float* raw, const float* raw_empty, const uint32_t* valid_bits, const float* z,
+                                             const float* rays_d, int R, int S, float B, const float* noise, float* rgb_map,
+                                             float* disp, float* acc, float* weights, float* alpha, const int32_t* ray_list,
+                                             const int32_t* ray_count, int act, float shift, void* stream) {
+    DANBO_CHECK_DENSITY_ACT(act, shift);
+    return act == DENSITY_SOFTPLUS
+               ? composite_impl<DENSITY_SOFTPLUS>(raw, raw_empty, valid_bits, z, rays_d, R, S, B, noise, rgb_map, disp, acc, weights, alpha,
+                                                  ray_list, ray_count, shift, stream)
+               : composite_impl<DENSITY_RELU>(raw, raw_empty, valid_bits, z, rays_d, R, S, B, noise, rgb_map, disp, acc, weights, alpha,
+                                              ray_list, ray_count, 0.f, stream);
 }
 
 template <bool TWO>
@@ -1548,29 +1483,29 @@ extern "C" int danbo_importance_samples_pdf(const float* z, const float* weights
                : importance_impl<false>(z, weights, R, S, Sf, u, z_fine, z_sorted, sorted_idx, ray_list, ray_count, stream);
 }
 
-template <bool TWO>
+template <bool TWO, int DA>
 static int composite_importance_impl(const float* raw, const float* raw_empty, const uint32_t* valid_bits, const float* z,
                                      const float* rays_d, int R, int S, int Sf, float B, const float* noise, const float* u,
                                      float* rgb_map, float* disp, float* acc, float* weights, float* alpha, float* z_fine,
                                      float* z_sorted, int32_t* sorted_idx, const int32_t* ray_list, const int32_t* ray_count,
-                                     void* stream) {
+                                     float shift, void* stream) {
     DANBO_CHECK_ARG(R > 0 && S >= 3 && S <= 64 && Sf > 0 && Sf <= 64 && B > 0.f);
     DANBO_CHECK_ARG(raw && z && rays_d && rgb_map && disp && acc && z_fine && z_sorted && sorted_idx);
     DANBO_CHECK_ARG((valid_bits == nullptr) || (raw_empty != nullptr));
     DANBO_CHECK_ARG((ray_list == nullptr) == (ray_count == nullptr));
-    static const int resident[2] = {resident_grid(k_composite_importance<false, TWO>, 1L << 40, 256),
-                                    resident_grid(k_composite_importance<true, TWO>, 1L << 40, 256)};
+    static const int resident[2] = {resident_grid(k_composite_importance<false, TWO, DA>, 1L << 40, 256),
+                                    resident_grid(k_composite_importance<true, TWO, DA>, 1L << 40, 256)};
     const dim3 grid((unsigned)std::min<long>(ceil_div((long)R * 64, 256), resident[u ? 0 : 1])), block(256);
     const float4* r4 = reinterpret_cast<const float4*>(raw);
     const float4* e4 = reinterpret_cast<const float4*>(raw_empty);
     if (u)
-        hipLaunchKernelGGL((k_composite_importance<false, TWO>), grid, block, 0, (hipStream_t)stream, r4, e4, valid_bits, z, rays_d,
+        hipLaunchKernelGGL((k_composite_importance<false, TWO, DA>), grid, block, 0, (hipStream_t)stream, r4, e4, valid_bits, z, rays_d,
                            R, S, Sf, B, noise, u, rgb_map, disp, acc, weights, alpha, z_fine, z_sorted, sorted_idx, ray_list, ray_count,
-                           ray_scatter(R));
+                           ray_scatter(R), shift);
     else
-        hipLaunchKernelGGL((k_composite_importance<true, TWO>), grid, block, 0, (hipStream_t)stream, r4, e4, valid_bits, z, rays_d,
+        hipLaunchKernelGGL((k_composite_importance<true, TWO, DA>), grid, block, 0, (hipStream_t)stream, r4, e4, valid_bits, z, rays_d,
                            R, S, Sf, B, noise, u, rgb_map, disp, acc, weights, alpha, z_fine, z_sorted, sorted_idx, ray_list, ray_count,
-                           ray_scatter(R));
+                           ray_scatter(R), shift);
     DANBO_LAUNCH_RET();
 }
 extern "C" int danbo_composite_importance_fwd(const float* raw, const float* raw_empty, const uint32_t* valid_bits,
@@ -1579,8 +1514,8 @@ extern "C" int danbo_composite_importance_fwd(const float* raw, const float* raw
                                                float* acc, float* weights, float* alpha, float* z_fine, float* z_sorted,
                                                int32_t* sorted_idx, const int32_t* ray_list, const int32_t* ray_count,
                                                void* stream) {
-    return composite_importance_impl<false>(raw, raw_empty, valid_bits, z, rays_d, R, S, Sf, B, noise, u, rgb_map, disp, acc, weights,
-                                            alpha, z_fine, z_sorted, sorted_idx, ray_list, ray_count, stream);
+    return composite_importance_impl<false, DENSITY_RELU>(raw, raw_empty, valid_bits, z, rays_d, R, S, Sf, B, noise, u, rgb_map, disp, acc,
+                                                          weights, alpha, z_fine, z_sorted, sorted_idx, ray_list, ray_count, 0.f, stream);
 }
 extern "C" int danbo_composite_importance_pdf_fwd(const float* raw, const float* raw_empty, const uint32_t* valid_bits,
                                                    const float* z, const float* rays_d, int R, int S, int Sf, float B,
@@ -1588,11 +1523,24 @@ extern "C" int danbo_composite_importance_pdf_fwd(const float* raw, const float*
                                                    float* acc, float* weights, float* alpha, float* z_fine, float* z_sorted,
                                                    int32_t* sorted_idx, const int32_t* ray_list, const int32_t* ray_count,
                                                    void* stream) {
+    return danbo_composite_importance_pdf_fwd_act(raw, raw_empty, valid_bits, z, rays_d, R, S, Sf, B, noise, u, pdf, rgb_map, disp, acc,
+                                                  weights, alpha, z_fine, z_sorted, sorted_idx, ray_list, ray_count, DENSITY_RELU, 0.f,
+                                                  stream);
+}
+extern "C" int danbo_composite_importance_pdf_fwd_act(const float* raw, const float* raw_empty, const uint32_t* valid_bits,
+                                                       const float* z, const float* rays_d, int R, int S, int Sf, float B,
+                                                       const float* noise, const float* u, int pdf, float* rgb_map, float* disp,
+                                                       float* acc, float* weights, float* alpha, float* z_fine, float* z_sorted,
+                                                       int32_t* sorted_idx, const int32_t* ray_list, const int32_t* ray_count,
+                                                       int act, float shift, void* stream) {
     DANBO_CHECK_ARG(pdf == 0 || pdf == 1);
-    return pdf ? composite_importance_impl<true>(raw, raw_empty, valid_bits, z, rays_d, R, S, Sf, B, noise, u, rgb_map, disp, acc,
-                                                 weights, alpha, z_fine, z_sorted, sorted_idx, ray_list, ray_count, stream)
-               : composite_importance_impl<false>(raw, raw_empty, valid_bits, z, rays_d, R, S, Sf, B, noise, u, rgb_map, disp, acc,
-                                                  weights, alpha, z_fine, z_sorted, sorted_idx, ray_list, ray_count, stream);
+    DANBO_CHECK_DENSITY_ACT(act, shift);
+#define DANBO_CI(TWO_, DA_, SH_)                                                                                                   \
+    composite_importance_impl<TWO_, DA_>(raw, raw_empty, valid_bits, z, rays_d, R, S, Sf, B, noise, u, rgb_map, disp, acc, weights, \
+                                         alpha, z_fine, z_sorted, sorted_idx, ray_list, ray_count, SH_, stream)
+    if (act == DENSITY_SOFTPLUS) return pdf ? DANBO_CI(true, DENSITY_SOFTPLUS, shift) : DANBO_CI(false, DENSITY_SOFTPLUS, shift);
+    return pdf ? DANBO_CI(true, DENSITY_RELU, 0.f) : DANBO_CI(false, DENSITY_RELU, 0.f);
+#undef DANBO_CI
 }
 
 extern "C" int danbo_flat_rays(const float* t_lo, const uint32_t* ray_flat, int R, int S, int Sf, float* rgb0, float* disp0, float* acc0, float* weights0, float* alpha0, float* z_fine,
@@ -1607,19 +1555,52 @@ extern "C" int danbo_flat_rays(const float* t_lo, const uint32_t* ray_flat, int 
     DANBO_LAUNCH_RET();
 }
 
+template <int DA>
+static int composite_merged_impl(const float* raw_a, const float* raw_b, const float* raw_empty,
+                                 const uint32_t* bits_a, const uint32_t* bits_b, const int32_t* sorted_idx,
+                                 const float* z_sorted, const float* rays_d, int R, int S, int Sf, float B,
+                                 const float* noise, float* rgb_map, float* disp, float* acc, float* weights,
+                                 float* alpha, float* raw_sorted, const int32_t* ray_list, const int32_t* ray_count,
+                                 float shift, void* stream) {
+    DANBO_CHECK_ARG(R > 0 && S > 0 && Sf > 0 && B > 0.f && raw_a && raw_b && sorted_idx && z_sorted && rays_d);
+    DANBO_CHECK_ARG(rgb_map && disp && acc && ((bits_a == nullptr && bits_b == nullptr) || raw_empty != nullptr));
+    DANBO_CHECK_ARG((ray_list == nullptr) == (ray_count == nullptr));
+    const float4 *a4 = reinterpret_cast<const float4*>(raw_a), *b4 = reinterpret_cast<const float4*>(raw_b);
+    const float4* e4 = reinterpret_cast<const float4*>(raw_empty);
+    float4* rs4 = reinterpret_cast<float4*>(raw_sorted);
+    if constexpr (DA == DENSITY_SOFTPLUS) {
+        static const int per_launch = resident_grid(k_composite_merged_softplus, 1L << 40, 256);
+        hipLaunchKernelGGL(k_composite_merged_softplus, dim3((unsigned)std::min<long>(ceil_div((long)R * 64, 256), per_launch)), dim3(256), 0,
+                           (hipStream_t)stream, a4, b4, e4, bits_a, bits_b, sorted_idx, z_sorted, rays_d, R, S, Sf, B, noise, rgb_map, disp, acc,
+                           weights, alpha, rs4, ray_list, ray_count, ray_scatter(R), shift);
+    } else {
+        static const int per_launch = resident_grid(k_composite_merged, 1L << 40, 256);
+        hipLaunchKernelGGL(k_composite_merged, dim3((unsigned)std::min<long>(ceil_div((long)R * 64, 256), per_launch)), dim3(256), 0,
+                           (hipStream_t)stream, a4, b4, e4, bits_a, bits_b, sorted_idx, z_sorted, rays_d, R, S, Sf, B, noise, rgb_map, disp, acc,
+                           weights, alpha, rs4, ray_list, ray_count, ray_scatter(R));
+    }
+    DANBO_LAUNCH_RET();
+}
 extern "C" int danbo_composite_merged_fwd(const float* raw_a, const float* raw_b, const float* raw_empty,
                                            const uint32_t* bits_a, const uint32_t* bits_b, const int32_t* sorted_idx,
                                            const float* z_sorted, const float* rays_d, int R, int S, int Sf, float B,
                                            const float* noise, float* rgb_map, float* disp, float* acc, float* weights,
                                            float* alpha, float* raw_sorted, const int32_t* ray_list, const int32_t* ray_count,
                                            void* stream) {
-    DANBO_CHECK_ARG(R > 0 && S > 0 && Sf > 0 && B > 0.f && raw_a && raw_b && sorted_idx && z_sorted && rays_d);
-    DANBO_CHECK_ARG(rgb_map && disp && acc && ((bits_a == nullptr && bits_b == nullptr) || raw_empty != nullptr));
-    DANBO_CHECK_ARG((ray_list == nullptr) == (ray_count == nullptr));
-    static const int per_launch = resident_grid(k_composite_merged, 1L << 40, 256);
-    hipLaunchKernelGGL(k_composite_merged, dim3((unsigned)std::min<long>(ceil_div((long)R * 64, 256), per_launch)), dim3(256), 0, (hipStream_t)stream,
-                       reinterpret_cast<const float4*>(raw_a), reinterpret_cast<const float4*>(raw_b),
-                       reinterpret_cast<const float4*>(raw_empty), bits_a, bits_b, sorted_idx, z_sorted, rays_d, R, S, Sf, B,
-                       noise, rgb_map, disp, acc, weights, alpha, reinterpret_cast<float4*>(raw_sorted), ray_list, ray_count, ray_scatter(R));
-    DANBO_LAUNCH_RET();
+    return composite_merged_impl<DENSITY_RELU>(raw_a, raw_b, raw_empty, bits_a, bits_b, sorted_idx, z_sorted, rays_d, R, S, Sf, B, noise,
+                                               rgb_map, disp, acc, weights, alpha, raw_sorted, ray_list, ray_count, 0.f, stream);
+}
+extern "C" int danbo_composite_merged_fwd_act(const float* raw_a, const float* raw_b, const float* raw_empty,
+                                               const uint32_t* bits_a, const uint32_t* bits_b, const int32_t* sorted_idx,
+                                               const float* z_sorted, const float* rays_d, int R, int S, int Sf, float B,
+                                               const float* noise, float* rgb_map, float* disp, float* acc, float* weights,
+                                               float* alpha, float* raw_sorted, const int32_t* ray_list, const int32_t* ray_count,
+                                               int act, float shift, void* stream) {
+    DANBO_CHECK_DENSITY_ACT(act, shift);
+    return act == DENSITY_SOFTPLUS
+               ? composite_merged_impl<DENSITY_SOFTPLUS>(raw_a, raw_b, raw_empty, bits_a, bits_b, sorted_idx, z_sorted, rays_d, R, S, Sf, B,
+                                                         noise, rgb_map, disp, acc, weights, alpha, raw_sorted, ray_list, ray_count, shift,
+                                                         stream)
+               : composite_merged_impl<DENSITY_RELU>(raw_a, raw_b, raw_empty, bits_a, bits_b, sorted_idx, z_sorted, rays_d, R, S, Sf, B,
+                                                     noise, rgb_map, disp, acc, weights, alpha, raw_sorted, ray_list, ray_count, 0.f, stream);
 }

@@ -137,6 +137,46 @@ DANBO_HD void gather_bone_features(VolPtr vol, const float* pt, const float* abs
 
 DANBO_HD float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// ---- density activation (get_density_fn, core/raycasters.py:192-200): relu(x) or softplus(x - shift) ----
+// A compile-time parameter of every composite (DA); the shift is a run-time float that the relu forms never read.
+constexpr int DENSITY_RELU = 0;
+constexpr int DENSITY_SOFTPLUS = 1;
+// log(1 + e^t) for t <= 20 (clamped: the caller's select drops the other side, and no inf or NaN is formed on the way).
+// Device: log(u) e / (u - 1) with u = fl(1 + e) -- the rounding of 1 + e cancels in the quotient (e itself where u == 1), a few
+// ulp like log1p.  Not the device library's log1pf: it sums its two-float result with a v_pk_add_f32 ... op_sel:[0,1], the packed
+// operand selection that is wrong on gfx950 beside MFMA wavefronts (common.hpp, DANBO_NO_PK_F32), and a kernel template cannot
+// carry that attribute for one of its instantiations only.
+DANBO_HD float log1p_exp(float t) {
+    const float e = expf(fminf(t, 20.f));
+#if defined(__HIP_DEVICE_COMPILE__)
+    const float u = add_rn(1.0f, e);
+    return u == 1.0f ? e : mul_rn(logf(u), div_rn(e, sub_rn(u, 1.0f)));
+#else
+    return log1pf(e);
+#endif
+}
+// F.softplus(x - shift, beta=1) with torch's threshold 20.  A NaN logit stays NaN, as in torch (the clamp inside log1p_exp would
+// drop it; relu's fmaxf makes it 0, as before)
+template <int DA>
+DANBO_HD float density_act(float x, float shift) {
+    if constexpr (DA == DENSITY_SOFTPLUS) {
+        const float t = sub_rn(x, shift);
+        return (t > 20.f || t != t) ? t : log1p_exp(t);
+    } else {
+        return fmaxf(x, 0.f);
+    }
+}
+// d density_act / d x: [x > 0] for relu; sigmoid(x - shift) (1 beyond the threshold) for softplus
+template <int DA>
+DANBO_HD float density_act_grad(float x, float shift) {
+    if constexpr (DA == DENSITY_SOFTPLUS) {
+        const float t = sub_rn(x, shift);
+        return t > 20.f ? 1.0f : sigmoidf_(t);
+    } else {
+        return x > 0.f ? 1.0f : 0.f;
+    }
+}
+
 // ---- get_near_far_in_cylinder, one ray, before the NaN back-fill ----------------------
 // core/utils/ray_utils.py:294-329.  Returns false when the ray misses the cylinder.
 DANBO_HD bool cylinder_bounds(const float* o, const float* d, const float* cyl, float near0, float far0,
@@ -267,8 +307,10 @@ DANBO_HD void importance_ray(const float* z, const float* w, int S, int Sf, cons
 }
 
 // ---- alpha compositing of one ray, sequential form (core/networks/nerf.py:281-347) -----
+// DA / shift: the density activation (density_act above); the default is relu, which never reads the shift
+template <int DA = DENSITY_RELU>
 DANBO_HD void composite_ray(const float* raw, const float* z, const float* d, int S, float B, const float* noise,
-                            float* rgb_map, float* disp, float* acc_out, float* weights, float* alpha_out) {
+                            float* rgb_map, float* disp, float* acc_out, float* weights, float* alpha_out, float shift = 0.f) {
     const float dn = norm3_torch(d[0], d[1], d[2]);
     float T = 1.0f, r = 0.f, g = 0.f, b = 0.f, depth = 0.f, acc = 0.f;
     for (int s = 0; s < S; ++s) {
@@ -276,7 +318,7 @@ DANBO_HD void composite_ray(const float* raw, const float* z, const float* d, in
         const float dist = mul_rn(dz, dn);
         float sg = div_rn(raw[4 * s + 3], B);
         if (noise) sg = add_rn(sg, noise[s]);
-        sg = fmaxf(sg, 0.f);
+        sg = density_act<DA>(sg, shift);
         const float al = sub_rn(1.0f, expf(-mul_rn(sg, dist)));
         const float w = mul_rn(al, T);
         T = mul_rn(T, add_rn(sub_rn(1.0f, al), 1e-10f));

@@ -28,6 +28,14 @@ extern "C" {
 #define DANBO_FEAT 15       /* voxel_feat * 3 ('cat' construct)                     */
 #define DANBO_H_STRIDE 16   /* blended feature rows are padded 15 -> 16 floats      */
 #define DANBO_RAY_FLAT_VMAX 1e4f /* danbo_ray_bone_mask flags no ray whose view direction inputs may exceed this */
+/* density activation of the `_act` entry points (get_density_fn, core/raycasters.py:192-200; --density_type / --softplus_shift,
+ * run_nerf.py:312-315), passed as two trailing scalars `int act, float shift` in front of the stream:
+ *   relu:     sigma = max(x, 0)                                          (shift is ignored)
+ *   softplus: sigma = F.softplus(x - shift, beta=1) = t > 20 ? t : log1p(exp(t)), t = x - shift
+ * with x = raw[..., 3] / B + noise.  Any other act, or a shift that is not finite, is DANBO_EINVAL before any launch.  Every
+ * entry point without the suffix is the relu form of its `_act` variant: same kernels, same arithmetic. */
+#define DANBO_DENSITY_RELU 0
+#define DANBO_DENSITY_SOFTPLUS 1
 
 /* library / device identification (host only).
  * ABI history: 2 = danbo_adam_step takes the step's scalars by value; 3 = DanboAssignBwd.d_p; 4 = danbo_train_workspace_view,
@@ -40,7 +48,9 @@ extern "C" {
  * building blocks; 9 = K3 in the 32x32x16 form (danbo_mlp32_pack, danbo_pe_mlp32_fwd: additive), danbo_view_consts' rgb_order 2;
  * danbo_render_frame runs it: DanboModel.mlp16 is a buffer packed by danbo_mlp32_pack (a caller of ABI 8 must re-pack); additive:
  * danbo_transform_batch_pts, danbo_optcodes_fwd (the reference's eager encoder helpers); danbo_importance_samples_pdf,
- * danbo_composite_importance_pdf_fwd (the pdf of the two-network mode, single_net = False). */
+ * danbo_composite_importance_pdf_fwd (the pdf of the two-network mode, single_net = False); danbo_composite_rays_fwd_act,
+ * danbo_composite_importance_pdf_fwd_act, danbo_composite_merged_fwd_act, danbo_composite_bwd_lazy_act, danbo_render_frame_act
+ * (the density activation: relu or softplus(x - shift), density_type = softplus). */
 int danbo_abi_version(void);
 int danbo_device_info(int* cu_count, int* lds_bytes, char* arch, int arch_len);
 
@@ -307,6 +317,14 @@ int danbo_composite_rays_fwd(const float* raw, const float* raw_empty /*[R,4]*/,
                              const float* rays_d, int R, int S, float B, const float* noise, float* rgb_map, float* disp,
                              float* acc, float* weights, float* alpha, const int32_t* ray_list, const int32_t* ray_count,
                              void* stream);
+/* danbo_composite_rays_fwd (and, with raw_empty / valid_bits / ray_list / ray_count NULL, danbo_composite_fwd) with a choice of
+ * density activation (additive in ABI 9): act_fn of NeRF.raw2outputs, core/networks/nerf.py:297
+ * `alpha = 1 - exp(-act_fn(raw / B + noise) * dists)`.  Under softplus the samples that take raw_empty[ray] contribute density
+ * like any other; a ray_list made by danbo_flat_rays must not be passed then (statement (a) there cannot hold). */
+int danbo_composite_rays_fwd_act(const float* raw, const float* raw_empty /*[R,4]*/, const uint32_t* valid_bits /*[R,S]*/,
+                                 const float* z, const float* rays_d, int R, int S, float B, const float* noise, float* rgb_map,
+                                 float* disp, float* acc, float* weights, float* alpha, const int32_t* ray_list,
+                                 const int32_t* ray_count, int act, float shift, void* stream);
 
 /* K4 backward: gradients of rgb_map [R,3] and acc_map [R] -> d raw [R,S,4] (S <= 256).  disp_map,
  * weights and alpha carry no gradient in the reference's losses (core/trainer.py:396-422,507-536). */
@@ -317,6 +335,12 @@ int danbo_composite_bwd(const float* raw, const float* z, const float* rays_d, i
 int danbo_composite_bwd_lazy(const float* raw, const float* raw_empty /*[R,4]*/, const uint32_t* valid_bits /*[R,S] or NULL*/,
                              const float* z, const float* rays_d, int R, int S, float B, const float* noise,
                              const float* g_rgb, const float* g_acc, float* d_raw, void* stream);
+/* danbo_composite_bwd_lazy (and, with raw_empty / valid_bits NULL, danbo_composite_bwd) with a choice of density activation
+ * (additive in ABI 9): the adjoint of core/networks/nerf.py:297 with d sigma / d x = [x > 0] (relu) or
+ * t > 20 ? 1 : sigmoid(t), t = x - shift (softplus) */
+int danbo_composite_bwd_lazy_act(const float* raw, const float* raw_empty /*[R,4]*/, const uint32_t* valid_bits /*[R,S] or NULL*/,
+                                 const float* z, const float* rays_d, int R, int S, float B, const float* noise,
+                                 const float* g_rgb, const float* g_acc, float* d_raw, int act, float shift, void* stream);
 
 /* K1b backward: d part_feat [n,24,15] -> d volumes [G,24,240] and d axis_scale [24,3] (both ACCUMULATED
  * with atomics: the caller zeroes them).  Same autograd semantics as the reference: the window is
@@ -370,6 +394,15 @@ int danbo_composite_importance_pdf_fwd(const float* raw /*[R,S,4]*/, const float
                                        float* acc, float* weights, float* alpha, float* z_fine, float* z_sorted,
                                        int32_t* sorted_idx, const int32_t* ray_list /*[R] or NULL*/,
                                        const int32_t* ray_count /*[1] or NULL*/, void* stream);
+/* danbo_composite_importance_pdf_fwd with a choice of density activation (additive in ABI 9; core/networks/nerf.py:297 in the
+ * coarse raw2outputs of render_rays, core/raycasters.py:334-337): bit for bit danbo_composite_rays_fwd_act followed by
+ * danbo_importance_samples_pdf.  The softplus form has no shortcut for rays without an in-volume sample. */
+int danbo_composite_importance_pdf_fwd_act(const float* raw /*[R,S,4]*/, const float* raw_empty /*[R,4]*/,
+                                           const uint32_t* valid_bits /*[R,S]*/, const float* z, const float* rays_d, int R, int S,
+                                           int Sf, float B, const float* noise, const float* u, int pdf, float* rgb_map,
+                                           float* disp, float* acc, float* weights, float* alpha, float* z_fine, float* z_sorted,
+                                           int32_t* sorted_idx, const int32_t* ray_list /*[R] or NULL*/,
+                                           const int32_t* ray_count /*[1] or NULL*/, int act, float shift, void* stream);
 
 /* Rays of constants (no reference counterpart; the values are the reference's).  ray_flat: the flags danbo_ray_bone_mask made
  * and danbo_bone_cull of the COARSE pass (same rays, depths, mask, interval) has passed on -- a set flag says the ray cannot
@@ -386,7 +419,8 @@ int danbo_composite_importance_pdf_fwd(const float* raw /*[R,S,4]*/, const float
  * danbo_composite_importance_fwd and danbo_composite_merged_fwd (any S, Sf; rays of more than 64 coarse samples:
  * danbo_composite_rays_fwd, danbo_importance_samples_rays, danbo_composite_merged_fwd).  All maps / alphas / weights of the frame are then bit-identical
  * to evaluating every ray; a caller that wants z_fine / z_sorted / sorted_idx / cview / raw_empty of every ray, density noise, or
- * cannot state (a) and (b), must not use it.
+ * cannot state (a) and (b), must not use it.  Statement (a) is about relu: under softplus (the `_act` entry points) the density of
+ * empty space is positive on every sample, no ray is a ray of constants and this call must not be used.
  * parts: 1 = the list and the per-ray outputs (a few us: what danbo_view_consts waits for), 2 = the per-sample rows (weights0 /
  * alpha0 / z_fine / weights / alpha: ~130 MB of a 512 x 512 frame, needed only by the composites' consumers), 3 = both. */
 int danbo_flat_rays(const float* t_lo /*[R]*/, const uint32_t* ray_flat /*[R]*/, int R, int S, int Sf, float* rgb0, float* disp0,
@@ -403,6 +437,14 @@ int danbo_composite_merged_fwd(const float* raw_a /*[R,S,4]*/, const float* raw_
                                float* alpha, float* raw_sorted /*[R,S+Sf,4] or NULL*/,
                                const int32_t* ray_list /*[R] or NULL: as danbo_composite_importance_fwd*/,
                                const int32_t* ray_count, void* stream);
+/* danbo_composite_merged_fwd with a choice of density activation (additive in ABI 9; core/networks/nerf.py:297 in the final
+ * raw2outputs of render_rays, core/raycasters.py:373-375): bit for bit danbo_merge_samples + danbo_composite_rays_fwd_act */
+int danbo_composite_merged_fwd_act(const float* raw_a /*[R,S,4]*/, const float* raw_b /*[R,Sf,4]*/, const float* raw_empty,
+                                   const uint32_t* bits_a, const uint32_t* bits_b, const int32_t* sorted_idx,
+                                   const float* z_sorted /*[R,S+Sf]*/, const float* rays_d, int R, int S, int Sf, float B,
+                                   const float* noise, float* rgb_map, float* disp, float* acc, float* weights /*[R,S+Sf]*/,
+                                   float* alpha, float* raw_sorted /*[R,S+Sf,4] or NULL*/, const int32_t* ray_list,
+                                   const int32_t* ray_count, int act, float shift, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * A-NeRF (nerf_type = nerf): the per-sample encoders around the W = 448 trunk.
@@ -892,6 +934,11 @@ size_t danbo_render_frame_workspace(int R, int G, int S, int Sf, int chunk, int 
 /* 3 <= S <= 256, Sf <= 64 (S <= 64: the fused composite + resampling launch).  Enqueues ~25 kernels on `stream`; workspace: danbo_render_frame_workspace bytes of device memory. */
 int danbo_render_frame(const DanboModel* model, const DanboRays* rays, int S, int Sf, const DanboFrameOut* out, void* workspace,
                        size_t workspace_bytes, void* stream);
+/* danbo_render_frame with a choice of density activation (additive in ABI 9; preproc_kwargs['density_fn'] of render_rays,
+ * core/raycasters.py:334-337,373-375 -- DanboModel has no field for it).  The softplus form ignores model->flat_rays_ok
+ * (statement (a) of danbo_flat_rays cannot hold) and evaluates every ray; relu is danbo_render_frame itself. */
+int danbo_render_frame_act(const DanboModel* model, const DanboRays* rays, int S, int Sf, const DanboFrameOut* out, void* workspace,
+                           size_t workspace_bytes, int act, float shift, void* stream);
 
 #ifdef __cplusplus
 }
