@@ -119,9 +119,13 @@ SIGNATURES = {
     "danbo_anerf_train_step": [P, P, P, P, c_size_t, P],
     "danbo_anerf_train_workspace_view": [P, I, I, I, I, I, P, P],
     "danbo_assign16_set_trace": [P],
+    # ---- isosurface extraction on the density grid
+    "danbo_mesh_workspace_bytes": [I, I, I],
+    "danbo_mesh_count": [P, I, I, I, c_long, c_long, F, F, P, P, P],
+    "danbo_mesh_extract": [P, I, I, I, c_long, c_long, F, F, P, F, F, F, F, P, I, P, I, P],
 }
 # everything else returns int (0 = ok)
-RESTYPES = {"danbo_render_frame_workspace": c_size_t, "danbo_train_workspace": c_size_t,
+RESTYPES = {"danbo_mesh_workspace_bytes": c_size_t, "danbo_render_frame_workspace": c_size_t, "danbo_train_workspace": c_size_t,
             "danbo_dw16_scratch_floats": c_long, "danbo_anerf_train_workspace": c_size_t,
             "danbo_anerf_view_consts_bwd_scratch_floats": c_long, "danbo_anerf_color_bwd_part_floats": c_long}
 

@@ -898,3 +898,35 @@ def _linear16_frag(x1, packed, shape, bias, relu, x2, out, count, fr):
     _call("danbo_linear16_fwd_frag", _p(a1), ld1, K1, _p(a2), ld2, K2, _p(packed), _p(_f32(bias, "bias")), N, 1 if relu else 0,
           _p(y), ldy, M, _p(count), fr, _stream())
     return out
+
+
+# -------------------------------------------------------------------------------------- isosurface extraction
+def marching_cubes(sigma, iso, floor=float("-inf"), scale=1.0, offset=(0.0, 0.0, 0.0)):
+    """Isosurface of a density grid in device memory (danbo_mesh_count / danbo_mesh_extract; the reference's
+    mcubes.marching_cubes, run_render.py:1279).  sigma [nx,ny,nz] float32 with innermost stride 1 -- the transposed view of
+    RayCaster.render_mesh_density is taken as it is, nothing is copied; every value is read as max(sigma, floor); inside = value >=
+    iso.  -> verts [V,3] float32 (index units * scale + offset, per axis), faces [T,3] int32, welded, in a deterministic order,
+    normals from inside to outside.  One host read (the two counts) sizes the outputs; an empty surface launches nothing more."""
+    if not sigma.is_cuda:
+        raise RuntimeError("sigma: expected a CUDA/HIP tensor -- libdanbo_hip has no CPU fallback")
+    if sigma.dtype != torch.float32 or sigma.dim() != 3:
+        raise ValueError("marching_cubes: sigma must be a [nx, ny, nz] float32 grid")
+    if sigma.stride(2) != 1:
+        raise ValueError("marching_cubes: the innermost stride of sigma must be 1")
+    nx, ny, nz = sigma.shape
+    grid = (_p(sigma), nx, ny, nz, sigma.stride(0), sigma.stride(1), float(floor), float(iso))
+    n_bytes = _hip.lib().danbo_mesh_workspace_bytes(nx, ny, nz)
+    if n_bytes == 0:
+        raise _hip.HipError(f"marching_cubes: unsupported grid {nx} x {ny} x {nz} (each dimension 2 .. 1024, fewer than 2^31 points)")
+    ws = torch.empty(n_bytes, device=sigma.device, dtype=torch.uint8)
+    counts = torch.empty(2, device=sigma.device, dtype=torch.int32)
+    _call("danbo_mesh_count", *grid, _p(ws), _p(counts), _stream())
+    V, T = counts.tolist()
+    if max(V, T) >= 2 ** 31 - 1:
+        raise _hip.HipError("marching_cubes: the surface has 2^31 or more vertices or triangles")
+    verts = torch.empty(V, 3, device=sigma.device, dtype=torch.float32)
+    faces = torch.empty(T, 3, device=sigma.device, dtype=torch.int32)
+    if V > 0:
+        ox, oy, oz = (float(x) for x in offset)
+        _call("danbo_mesh_extract", *grid, _p(ws), float(scale), ox, oy, oz, _p(verts), V, _p(faces), T, _stream())
+    return verts, faces

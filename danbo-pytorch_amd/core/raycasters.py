@@ -216,6 +216,8 @@ class RayCaster(nn.Module):
             return self.render_pts_density(*args, **kwargs)
         if fwd_type == 'mesh':
             return self.render_mesh_density(*args, **kwargs)
+        if fwd_type == 'mesh_surface':
+            return self.render_mesh_surface(*args, **kwargs)
         if fwd_type:
             raise NotImplementedError(fwd_type)
         if self.training:
@@ -416,6 +418,16 @@ class RayCaster(nn.Module):
         grid = torch.tensor(np.stack(np.meshgrid(t, t, t), axis=-1).astype(np.float32), device=kps.device)
         dens = self.render_pts_density(grid.reshape(-1, 3) + kps[0, 0], kps, skts, bones, netchunk)[..., :1]
         return dens.reshape(*grid.shape[:-1]).transpose(1, 0)      # x-y swapped, as the mesh extraction expects
+
+    @torch.no_grad()
+    def render_mesh_surface(self, kps, skts, bones, threshold=10., res=64, return_density=False, **kwargs):
+        """The density grid of render_mesh_density and its isosurface at `threshold`, as the reference's render_mesh makes it
+        (run_render.py:1278-1280): marching cubes on np.maximum(raw, 0), vertices / res - .5 per axis of the returned (x-y swapped)
+        array.  The grid stays on the device and is read through its transposed view.
+        -> verts [V,3] float32, faces [T,3] int32 (device tensors) [, the raw density grid]"""
+        dens = self.render_mesh_density(kps, skts, bones, res=res, **kwargs)
+        verts, faces = ops.marching_cubes(dens, float(threshold), floor=0., scale=1. / res, offset=(-.5, -.5, -.5))
+        return (verts, faces, dens) if return_density else (verts, faces)
 
 
 class _GraphCache:

@@ -24,6 +24,7 @@ from core.config import config_parser as nerf_config_parser, txt_to_argstring  #
 from core.load_data import PoseImageDataset, generate_bullet_time, get_dataset  # noqa: E402
 from core.raycasters import create_raycaster  # noqa: E402
 from core.utils.evaluation_helpers import evaluate_in_boxes  # noqa: E402
+from core.utils.mesh_io import write_ply  # noqa: E402
 from core.utils.skeleton_utils import get_smpl_l2ws  # noqa: E402
 from run_nerf import render_path  # noqa: E402
 
@@ -40,6 +41,7 @@ def config_parser():
     p.add_argument('--render_mesh', action='store_true', help='sample the density grid instead of rendering images')
     p.add_argument('--mesh_res', type=int, default=255)
     p.add_argument('--mesh_radius', type=float, default=1.8)
+    p.add_argument('--mesh_threshold', type=float, default=10.0, help='density of the extracted isosurface')
     p.add_argument('--render_confd', action='store_true')
     p.add_argument('--render_entropy', action='store_true')
     p.add_argument('--selected_idxs', nargs='+', type=int, default=None)
@@ -253,16 +255,19 @@ def evaluate_metric(rgbs, accs, bboxes, gt_dict, basedir):
 
 
 @torch.no_grad()
-def render_mesh(basedir, render_kwargs, tensor_data, chunk=4096, radius=1.80, res=255):
-    """Density on a (res+1)^3 grid around every pose (reference :1266-1281).  Marching cubes (PyMCubes / trimesh) is a host
-    step outside this image: the clamped grids are saved as `meshes/NNN_sigma.npy` for it."""
+def render_mesh(basedir, render_kwargs, tensor_data, chunk=4096, radius=1.80, res=255, threshold=10.):
+    """Density on a (res+1)^3 grid around every pose and its isosurface at `threshold` (reference :1266-1281: PyMCubes and trimesh
+    there, the library's own extraction kernels and core/utils/mesh_io.py here): `meshes/NNN.ply`, vertices in [-0.5, 0.5]^3, and
+    the clamped grid as `meshes/NNN_sigma.npy`."""
     caster = render_kwargs['ray_caster']
     os.makedirs(os.path.join(basedir, 'meshes'), exist_ok=True)
     kps, skts, bones = tensor_data['kp'], tensor_data['skts'], tensor_data['bones']
     for i in range(len(kps)):
-        raw = caster(kps=kps[i:i + 1], skts=skts[i:i + 1], bones=bones[i:i + 1], radius=radius,
-                     render_kwargs=render_kwargs['preproc_kwargs'], res=res, netchunk=chunk, fwd_type='mesh')
+        verts, faces, raw = caster(kps=kps[i:i + 1], skts=skts[i:i + 1], bones=bones[i:i + 1], radius=radius,
+                                   render_kwargs=render_kwargs['preproc_kwargs'], res=res, netchunk=chunk, threshold=threshold,
+                                   return_density=True, fwd_type='mesh_surface')
         np.save(os.path.join(basedir, 'meshes', f'{i:03d}_sigma.npy'), np.maximum(raw.cpu().numpy(), 0))
+        write_ply(os.path.join(basedir, 'meshes', f'{i:03d}.ply'), verts, faces)
 
 
 def run_render(argv=None):
@@ -278,7 +283,7 @@ def run_render(argv=None):
     basedir = os.path.join(args.outputdir, args.runname)
     os.makedirs(basedir, exist_ok=True)
     if args.render_mesh:
-        render_mesh(basedir, render_kwargs, tensor_data, res=args.mesh_res, radius=args.mesh_radius)
+        render_mesh(basedir, render_kwargs, tensor_data, res=args.mesh_res, radius=args.mesh_radius, threshold=args.mesh_threshold)
         return None
     render_kwargs = dict(render_kwargs, render_confd=args.render_confd, render_entropy=args.render_entropy)
     rgbs, _, accs, _, bboxes = render_path(render_kwargs=render_kwargs, chunk=nerf_args.chunk, ext_scale=nerf_args.ext_scale,

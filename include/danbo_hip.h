@@ -50,7 +50,8 @@ extern "C" {
  * danbo_transform_batch_pts, danbo_optcodes_fwd (the reference's eager encoder helpers); danbo_importance_samples_pdf,
  * danbo_composite_importance_pdf_fwd (the pdf of the two-network mode, single_net = False); danbo_composite_rays_fwd_act,
  * danbo_composite_importance_pdf_fwd_act, danbo_composite_merged_fwd_act, danbo_composite_bwd_lazy_act, danbo_render_frame_act
- * (the density activation: relu or softplus(x - shift), density_type = softplus). */
+ * (the density activation: relu or softplus(x - shift), density_type = softplus); danbo_mesh_workspace_bytes, danbo_mesh_count,
+ * danbo_mesh_extract (isosurface extraction on the density grid: --render_mesh ends in a mesh). */
 int danbo_abi_version(void);
 int danbo_device_info(int* cu_count, int* lds_bytes, char* arch, int arch_len);
 
@@ -939,6 +940,30 @@ int danbo_render_frame(const DanboModel* model, const DanboRays* rays, int S, in
  * (statement (a) of danbo_flat_rays cannot hold) and evaluates every ray; relu is danbo_render_frame itself. */
 int danbo_render_frame_act(const DanboModel* model, const DanboRays* rays, int S, int Sf, const DanboFrameOut* out, void* workspace,
                            size_t workspace_bytes, int act, float shift, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Isosurface extraction on a density grid in device memory (additive in ABI 9).  Replaces the host step of render_mesh
+ * (run_render.py:1265-1281): mcubes.marching_cubes(np.maximum(raw_d, 0), threshold), vertices / res - .5.
+ *   sigma: grid [nx][ny][nz], element (i, j, k) at sigma[i * stride_x + j * stride_y + k] (strides in elements, innermost 1: the
+ *   transposed view of RayCaster.render_mesh_density is read as it is).  Every value is read as s = fmaxf(sigma, floor) (floor = 0:
+ *   the reference's clamp; -INFINITY: none), a NaN as -inf; a point is inside iff s >= iso.  One welded vertex per grid edge whose
+ *   ends differ, at p + t e_ax, t = (iso - s0) / (s1 - s0) clamped to [0, 1] (0.5 where it is not finite), written as
+ *   v * scale + off (per axis: fma(t, scale, fma(p, scale, off)), two roundings).  Vertices ascend by (linear index of the lower end) * 3 + axis, triangles by the
+ *   cell's linear index ((i * ny + j) * nz + k), then in the order of csrc/mc_table.inc; normals point from inside to outside.  Two
+ *   runs give the same bits (nothing is ordered by atomics).
+ * danbo_mesh_count fills `workspace` (danbo_mesh_workspace_bytes: 4 B per grid point + 8 B per 256 points) and leaves the number
+ * of vertices and triangles in counts[0..1] (device; saturating at INT_MAX).  The caller reads them -- the one synchronisation of the
+ * path, it sizes the outputs -- and passes the same grid and workspace to danbo_mesh_extract, which writes verts [V,3] and
+ * tris [T,3] (int32 vertex indices) and nothing at or beyond cap_v / cap_t rows (a capacity of 0: that output is skipped and its
+ * pointer may be NULL).  DANBO_EINVAL before any launch: a dimension outside 2 .. 1024, nx * ny * nz >= 2^31, a negative stride,
+ * iso / scale / off not finite, floor NaN or +inf, a negative capacity, a null or misaligned pointer.
+ * ------------------------------------------------------------------------------------- */
+size_t danbo_mesh_workspace_bytes(int nx, int ny, int nz);
+int danbo_mesh_count(const float* sigma, int nx, int ny, int nz, long stride_x, long stride_y, float floor, float iso,
+                     void* workspace, int* counts /* device [2]: vertices, triangles */, void* stream);
+int danbo_mesh_extract(const float* sigma, int nx, int ny, int nz, long stride_x, long stride_y, float floor, float iso,
+                       const void* workspace, float scale, float off_x, float off_y, float off_z,
+                       float* verts /*[cap_v,3]*/, int cap_v, int* tris /*[cap_t,3]*/, int cap_t, void* stream);
 
 #ifdef __cplusplus
 }

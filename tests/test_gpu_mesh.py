@@ -1,0 +1,320 @@
+"""Isosurface extraction on the GPU (csrc/k_mesh.hip through hip_ops.marching_cubes, RayCaster fwd_type='mesh_surface',
+run_render --render_mesh): the kernels against the serial extractor of csrc/mesh_math.hpp bit for bit -- vertices, faces, order --
+and the real density grid of the danbo_mesh golden's pose against the numpy predictions of tests/mesh_ref.py."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import mesh_ref as m
+from helpers import ROOT, golden
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+F32 = np.float32
+
+
+def T(x, dtype=torch.float32):
+    return torch.tensor(np.ascontiguousarray(x), dtype=dtype, device=DEV)
+
+
+def gpu_extract(sigma_t, iso, floor=-np.inf, scale=1.0, offset=(0., 0., 0.)):
+    from core import hip_ops
+    v, f = hip_ops.marching_cubes(sigma_t, iso, floor=floor, scale=scale, offset=offset)
+    assert v.dtype == torch.float32 and f.dtype == torch.int32 and v.is_cuda and f.is_cuda
+    assert v.dim() == 2 and v.shape[1] == 3 and f.dim() == 2 and f.shape[1] == 3
+    return v.cpu().numpy(), f.cpu().numpy()
+
+
+def same_bits(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+def grids():
+    import test_mesh_extract as cpu
+    out = cpu.all_cases()
+    rng = np.random.default_rng(21)
+    out["2x2x2"] = (np.array([[[1., -1.], [-1., -1.]], [[-1., -1.], [-1., 2.]]], F32), 0., -np.inf)
+    out["3x5x130"] = (rng.standard_normal((3, 5, 130)).astype(F32), 0.1, -np.inf)
+    out["65x33x17"] = (m.sphere_grid((65, 33, 17), R=7.4, centre=(30.2, 15.7, 8.1)), 0., -np.inf)
+    out["65x33x17 noise"] = (rng.standard_normal((65, 33, 17)).astype(F32), 0.3, -np.inf)
+    out["negative floored"] = ((rng.standard_normal((31, 18, 67)) * 5 - 1).astype(F32), 2., 0.)
+    wild = (rng.standard_normal((20, 21, 22)) * 4).astype(F32)
+    wild.ravel()[rng.choice(wild.size, 300, replace=False)] = np.nan
+    wild.ravel()[rng.choice(wild.size, 300, replace=False)] = np.inf
+    wild.ravel()[rng.choice(wild.size, 300, replace=False)] = -np.inf
+    out["nan / inf"] = (wild, 0.5, -np.inf)
+    out["constant"] = (np.full((9, 9, 9), F32(1.)), 2., -np.inf)
+    return out
+
+
+# ----------------------------------------------------------------------------- 7. kernels = serial extractor, bit for bit
+@pytest.mark.parametrize("name", sorted(grids()))
+def test_kernels_equal_the_serial_extractor_bitwise(name):
+    sigma, iso, floor = grids()[name]
+    hv, hf = m.host_extract(np.ascontiguousarray(sigma), iso, floor)
+    gv, gf = gpu_extract(T(sigma), iso, floor)
+    print(name, "V", len(hv), "T", len(hf))
+    assert same_bits(gv, hv) and same_bits(gf, hf)
+    if len(hv) == 0:
+        assert gv.shape == (0, 3) and gf.shape == (0, 3)
+
+
+def test_large_sphere_views_transform_streams_and_replays():
+    n = 256
+    sphere = m.sphere_grid((n, n, n), R=100.3, centre=(127.3, 128.6, 126.1))
+    st = T(sphere)
+    hv, hf = m.host_extract(sphere, 0.)
+    gv, gf = gpu_extract(st, 0.)
+    print("256^3 sphere: V", len(hv), "T", len(hf))
+    assert len(hv) > 100000 and same_bits(gv, hv) and same_bits(gf, hf)
+    gv2, gf2 = gpu_extract(st, 0.)                                     # a replay gives the same bits
+    assert same_bits(gv2, gv) and same_bits(gf2, gf)
+    # the x-y swapped view of render_mesh_density, read through its strides, against the extractor on a contiguous copy
+    rng = np.random.default_rng(3)
+    base = (rng.standard_normal((37, 41, 29)) + m.sphere_grid((37, 41, 29), R=11., centre=(17., 20., 14.)) * 0.5).astype(F32)
+    view = T(base).transpose(1, 0)
+    assert not view.is_contiguous() and view.stride(2) == 1
+    hv, hf = m.host_extract(np.ascontiguousarray(base.transpose(1, 0, 2)), 0.2)
+    gv, gf = gpu_extract(view, 0.2)
+    assert len(hv) > 1000 and same_bits(gv, hv) and same_bits(gf, hf)
+    hv_s, hf_s = m.host_extract(base.transpose(1, 0, 2), 0.2)          # the serial extractor reads strides too
+    assert same_bits(hv_s, hv) and same_bits(hf_s, hf)
+    # floor = 0 on a grid with negative values moves t on every edge whose outer end is negative
+    neg = (base * 4 - 1).astype(F32)
+    hv0, hf0 = m.host_extract(neg, 1.5, 0.)
+    gv0, gf0 = gpu_extract(T(neg), 1.5, 0.)
+    assert same_bits(gv0, hv0) and same_bits(gf0, hf0)
+    hv1, _ = m.host_extract(neg, 1.5)
+    assert hv1.shape == hv0.shape and not np.array_equal(hv1, hv0)
+    # scale / offset in the vertex kernel
+    hv, hf = m.host_extract(base, 0.2, scale=1. / 36, offset=(-.5, .125, 3.))
+    gv, gf = gpu_extract(T(base), 0.2, scale=1. / 36, offset=(-.5, .125, 3.))
+    assert same_bits(gv, hv) and same_bits(gf, hf)
+    # a non-default stream
+    torch.cuda.synchronize()
+    tb = T(base)
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        sv, sf = gpu_extract(tb, 0.2, scale=1. / 36, offset=(-.5, .125, 3.))
+    s.synchronize()
+    assert same_bits(sv, hv) and same_bits(sf, hf)
+    from core import hip_ops
+    with pytest.raises(ValueError, match="innermost stride"):
+        hip_ops.marching_cubes(T(base).transpose(1, 2), 0.2)
+    with pytest.raises(ValueError):
+        hip_ops.marching_cubes(T(base).double(), 0.2)
+
+
+GUARD = 0x5AFEC0DE
+
+
+def _raw_calls(sigma_t, iso, floor, cap=None):
+    """danbo_mesh_count + danbo_mesh_extract through ctypes with guard words behind the workspace and the outputs
+    -> verts, tris (numpy, the cap rows), V, T"""
+    from core import _hip
+    lib = _hip.lib()
+    nx, ny, nz = sigma_t.shape
+    n_bytes = lib.danbo_mesh_workspace_bytes(nx, ny, nz)
+    assert n_bytes % 4 == 0
+    ws = torch.full((n_bytes // 4 + 16,), GUARD, dtype=torch.int32, device=DEV)
+    counts = torch.full((2 + 16,), GUARD, dtype=torch.int32, device=DEV)
+    P = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    grid = (P(sigma_t), nx, ny, nz, sigma_t.stride(0), sigma_t.stride(1), floor, iso)
+    assert lib.danbo_mesh_count(*grid, P(ws), P(counts), st) == 0
+    V, Tn = counts[:2].tolist()
+    assert torch.all(counts[2:] == GUARD) and torch.all(ws[n_bytes // 4:] == GUARD)
+    cap_v, cap_t = (V, Tn) if cap is None else cap
+    verts = torch.full((3 * cap_v + 16,), float("nan"), dtype=torch.float32, device=DEV)
+    tris = torch.full((3 * cap_t + 16,), GUARD, dtype=torch.int32, device=DEV)
+    ws_before = ws.clone()
+    assert lib.danbo_mesh_extract(*grid, P(ws), 1.0, 0., 0., 0., P(verts), cap_v, P(tris), cap_t, st) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(ws, ws_before)
+    assert torch.all(torch.isnan(verts[3 * cap_v:])) and torch.all(tris[3 * cap_t:] == GUARD), "a write at or beyond the capacity"
+    return verts[:3 * cap_v].reshape(-1, 3).cpu().numpy(), tris[:3 * cap_t].reshape(-1, 3).cpu().numpy(), V, Tn
+
+
+def test_short_capacities_and_rejected_arguments():
+    from core import _hip
+    lib = _hip.lib()
+    sigma = m.noise_grid(4, (33, 29, 70))
+    st = T(sigma)
+    hv, hf = m.host_extract(sigma, 0.)
+    v, f, V, Tn = _raw_calls(st, 0., -np.inf)
+    assert (V, Tn) == (len(hv), len(hf)) and same_bits(v, hv) and same_bits(f, hf)
+    for cap in ((V - 1, Tn - 1), (V // 2, Tn // 3), (1, 1), (0, Tn), (V, 0)):
+        v, f, V2, T2 = _raw_calls(st, 0., -np.inf, cap)
+        assert (V2, T2) == (V, Tn) and same_bits(v, hv[:cap[0]]) and same_bits(f, hf[:cap[1]]), cap
+    # wrong arguments: DANBO_EINVAL, nothing launched (the outputs keep their fill)
+    nx, ny, nz = sigma.shape
+    ws = torch.full((lib.danbo_mesh_workspace_bytes(nx, ny, nz) // 4,), GUARD, dtype=torch.int32, device=DEV)
+    counts = torch.full((2,), GUARD, dtype=torch.int32, device=DEV)
+    verts = torch.full((3 * V,), float("nan"), dtype=torch.float32, device=DEV)
+    tris = torch.full((3 * Tn,), GUARD, dtype=torch.int32, device=DEV)
+    P = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())      # noqa: E731
+    nan, inf = float("nan"), float("inf")
+    good = dict(sigma=st, nx=nx, ny=ny, nz=nz, sx=ny * nz, sy=nz, floor=-inf, iso=0., ws=ws, counts=counts, scale=1., ox=0., oy=0., oz=0.,
+                verts=verts, cap_v=V, tris=tris, cap_t=Tn)
+
+    def count(**kw):
+        a = {**good, **kw}
+        return lib.danbo_mesh_count(P(a["sigma"]), a["nx"], a["ny"], a["nz"], a["sx"], a["sy"], a["floor"], a["iso"], P(a["ws"]),
+                                    P(a["counts"]), None)
+
+    def extract(**kw):
+        a = {**good, **kw}
+        return lib.danbo_mesh_extract(P(a["sigma"]), a["nx"], a["ny"], a["nz"], a["sx"], a["sy"], a["floor"], a["iso"], P(a["ws"]),
+                                      a["scale"], a["ox"], a["oy"], a["oz"], P(a["verts"]), a["cap_v"], P(a["tris"]), a["cap_t"], None)
+
+    for kw in (dict(sigma=None), dict(ws=None), dict(nx=1), dict(ny=1025), dict(nz=0), dict(sx=-1), dict(sy=-1), dict(iso=nan),
+               dict(iso=-inf), dict(floor=nan), dict(floor=inf)):
+        assert count(**kw) == -22 and extract(**kw) == -22, kw
+    assert count(counts=None) == -22
+    for kw in (dict(cap_v=-1), dict(cap_t=-1), dict(verts=None), dict(tris=None), dict(scale=nan), dict(ox=inf), dict(oy=nan),
+               dict(oz=-inf)):
+        assert extract(**kw) == -22, kw
+    torch.cuda.synchronize()
+    assert torch.all(ws == GUARD) and torch.all(counts == GUARD) and torch.all(torch.isnan(verts)) and torch.all(tris == GUARD)
+
+
+# ----------------------------------------------------------------------------- 8. the real thing
+_POSE = {}
+
+
+def golden_pose_surface():
+    """the danbo_mesh golden's pose at res 64 through the caster: density grid, threshold = the median of its positive values (an
+    untrained synthetic network need not reach the reference's 10), the surface at it"""
+    if not _POSE:
+        from test_gpu_modules import build
+        g = golden("danbo_mesh")
+        caster, kw = build("h36m_zju/danbo_base.txt", g)
+        res = 64
+        args = (T(g["kps"][:1]), T(g["skts"][:1]), T(g["bones"][:1]))
+        dens = caster(*args, fwd_type="mesh", radius=float(g["radius"]), res=res)
+        assert tuple(dens.shape) == (res + 1,) * 3 and not dens.is_contiguous()
+        grid = dens.cpu().numpy()
+        thr = float(F32(np.median(grid[grid > 0])))
+        verts, faces, dens2 = caster(*args, fwd_type="mesh_surface", radius=float(g["radius"]), res=res, threshold=thr,
+                                     return_density=True)
+        assert torch.equal(dens2, dens)
+        _POSE.update(res=res, dens=dens, sigma=np.ascontiguousarray(grid), thr=thr, v=verts.cpu().numpy(), f=faces.cpu().numpy())
+    return _POSE
+
+
+def test_surface_of_the_golden_pose_through_the_caster():
+    """The vertices are the crossing edges of np.maximum(grid, 0) at v / res - 0.5 (within 5e-7 of the float64 expression: check 1's
+    index-space bound divided by res, the rounding of 1 / res, two roundings of numbers <= 1), the surface is closed and oriented up
+    to the grid boundary and lies in [-0.5, 0.5]^3."""
+    from core import hip_ops
+    r = golden_pose_surface()
+    res, sigma, thr, v, f = r["res"], r["sigma"], r["thr"], r["v"], r["f"]
+    inside, p, ax = m.crossing_edges(sigma, thr, 0.)
+    print("golden pose: threshold", thr, "V", len(v), "T", len(f), "inside", int(inside.sum()))
+    assert len(v) == len(p) > 500 and len(f) > 1000
+    pos, s0, s1 = m.vertex_positions_f64(sigma, thr, 0., p, ax)
+    e = np.abs(v.astype(np.float64) - (pos / res - 0.5)).max()
+    print("golden pose: |v - (v_index / res - 0.5)| max", e)
+    assert e <= 5e-7
+    assert v.min() >= -0.5 and v.max() <= 0.5
+    # bit for bit the serial extractor with the same transform
+    hv, hf = m.host_extract(sigma, thr, 0., scale=1. / res, offset=(-.5, -.5, -.5))
+    assert same_bits(v, hv) and same_bits(f, hf)
+    # index units: check 1
+    vi, fi = (t.cpu().numpy() for t in hip_ops.marching_cubes(r["dens"], thr, floor=0.))
+    assert same_bits(fi, f)
+    assert np.all(np.abs(vi.astype(np.float64) - pos) <= 3e-7 + 1.2e-7 * np.abs(pos))
+    # closed and oriented up to the grid boundary
+    de = m.directed_edges(f)
+    on_boundary = np.any((vi == 0.) | (vi == float(res)), axis=1)
+    unmatched = [(a, b) for (a, b), n in de.items() if de.get((b, a), 0) != n]
+    print("golden pose: directed edges", sum(de.values()), "unmatched (boundary)", len(unmatched), "max multiplicity", max(de.values()))
+    assert all(on_boundary[a] and on_boundary[b] for a, b in unmatched)
+    assert np.all((f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 0] != f[:, 2]))
+
+
+def _interpolation_residual(sigma, thr, vi):
+    """|s0 + (s1 - s0) t_v - thr| / max(|s0|, |s1|) per vertex, t_v read off the index-space vertex (float64 evaluation)"""
+    _, p, ax = m.crossing_edges(sigma, thr, 0.)
+    assert len(p) == len(vi)
+    _, s0, s1 = m.vertex_positions_f64(sigma, thr, 0., p, ax)
+    k = np.arange(len(p))
+    t_v = vi.astype(np.float64)[k, ax] - p[k, ax]
+    return np.abs(s0 + (s1 - s0) * t_v - thr) / np.maximum(np.abs(s0), np.abs(s1))      # (one end is >= thr > 0)
+
+
+def test_interpolated_density_at_the_vertices_of_the_golden_pose():
+    """For every vertex of the caster's result the density interpolated linearly between its edge's two grid values, at the vertex,
+    equals the threshold within 1e-6 max(|s0|, |s1|) -- the bound as the issue derives it: the 1.8e-7 of t times |s1 - s0|.
+
+    What a float32 vertex can carry: the caster's coordinate is fma(t, 1/64, p/64 - 0.5) -- the lower end exact, ONE rounding of a
+    number below 0.5, i.e. up to 2^-26 = 1.5e-8, which is 64 * 2^-26 = 9.5e-7 of t -- so the worst case by reasoning is
+    (9.5e-7 + 1.8e-7) |s1 - s0| <= 1.13e-6 max(|s0|, |s1|): 13 % above the bound, reached only where the outer end is 0, the vertex
+    lies in the outer half of the box and both roundings fall badly.  (The first form of the vertex kernel, fl(fl(p + t) / 64) - 0.5,
+    rounded p + t in [32, 64) to 3.8e-6 and measured 1.92e-6 here: 953 of 16 784 vertices above the bound.)  The bound is as stated."""
+    r = golden_pose_surface()
+    res, sigma, thr = r["res"], r["sigma"], r["thr"]
+    _, p, ax = m.crossing_edges(sigma, thr, 0.)
+    assert len(p) == len(r["v"])
+    _, s0, s1 = m.vertex_positions_f64(sigma, thr, 0., p, ax)
+    k = np.arange(len(p))
+    t_v = (r["v"].astype(np.float64)[k, ax] + 0.5) * res - p[k, ax]
+    rel = np.abs(s0 + (s1 - s0) * t_v - thr) / np.maximum(np.abs(s0), np.abs(s1))      # (one end is >= thr > 0)
+    print("golden pose: |interpolated density - threshold| / max(|s0|, |s1|): max", rel.max(), "median", np.median(rel),
+          "vertices above 1e-6:", int((rel > 1e-6).sum()), "of", len(rel))
+    assert rel.max() <= 1e-6
+
+
+def test_interpolated_density_on_blocks_of_the_golden_pose():
+    """The same residual and the same bound with the float32 vertex able to carry t: the grid cut into 17^3 blocks (strided views,
+    every grid edge lies in at least one), so p < 16 and p + t is rounded to 4.8e-7 at most -- every vertex of every block within
+    1e-6 max(|s0|, |s1|)."""
+    from core import hip_ops
+    r = golden_pose_surface()
+    worst, n = 0., 0
+    for i in range(0, r["res"], 16):
+        for j in range(0, r["res"], 16):
+            for k in range(0, r["res"], 16):
+                view = r["dens"][i:i + 17, j:j + 17, k:k + 17]
+                vi, _ = (t.cpu().numpy() for t in hip_ops.marching_cubes(view, r["thr"], floor=0.))
+                if len(vi):
+                    rel = _interpolation_residual(r["sigma"][i:i + 17, j:j + 17, k:k + 17], r["thr"], vi)
+                    worst, n = max(worst, float(rel.max())), n + len(vi)
+    print("golden pose in 17^3 blocks: |interpolated density - threshold| / max(|s0|, |s1|) max", worst, "over", n, "vertices")
+    assert n >= len(r["v"]) and worst <= 1e-6
+
+
+# ----------------------------------------------------------------------------- 9. entry point
+def test_run_render_writes_the_ply(tmp_path):
+    import run_nerf
+    import run_render
+    from core.utils.mesh_io import read_ply
+    cfg = os.path.join(ROOT, "danbo-pytorch_amd", "configs", "surreal", "danbo_fast.txt")
+    run_nerf.train(["--config", cfg, "--basedir", str(tmp_path), "--expname", "demo", "--syn_poses", "2", "--syn_cams", "2",
+                    "--syn_res", "32", "--syn_rest_scale", "0.714", "--N_rand", "512", "--N_sample_images", "4", "--i_print", "10",
+                    "--i_weights", "20", "--i_testset", "20", "--render_factor", "0", "--n_iters", "20"])
+    log = tmp_path / "demo"
+    base = ["--nerf_args", str(log / "args.txt"), "--ckptpath", str(log / "000020.tar"), "--dataset", "synthetic", "--entry", "val",
+            "--outputdir", str(tmp_path / "out"), "--render_type", "selected", "--selected_idxs", "1", "--render_mesh", "--mesh_res", "15",
+            "--mesh_radius", "1.2"]
+    run_render.run_render(base + ["--runname", "first"])                       # the reference's threshold, 10
+    d = tmp_path / "out" / "first" / "meshes"
+    sig = np.load(d / "000_sigma.npy")
+    assert sig.shape == (16, 16, 16) and sig.min() >= 0 and sig.max() > 0
+    v, f = read_ply(str(d / "000.ply"))
+    assert len(v) == len(m.crossing_edges(sig, 10.)[1])
+    thr = float(F32(np.median(sig[sig > 0])))
+    run_render.run_render(base + ["--runname", "second", "--mesh_threshold", repr(thr)])
+    d = tmp_path / "out" / "second" / "meshes"
+    sig2 = np.load(d / "000_sigma.npy")
+    assert np.array_equal(sig2, sig)
+    v, f = read_ply(str(d / "000.ply"))
+    _, p, ax = m.crossing_edges(sig, thr)
+    print("run_render mesh: threshold", thr, "V", len(v), "T", len(f))
+    assert len(v) == len(p) > 0 and len(f) > 0 and f.max() < len(v)
+    assert v.min() >= -0.5 and v.max() <= 0.5
+    hv, hf = m.host_extract(sig, thr, scale=1. / 15, offset=(-.5, -.5, -.5))
+    assert same_bits(v, hv) and same_bits(f, hf)
