@@ -8,6 +8,8 @@ import ctypes
 import os
 from ctypes import c_long, c_char_p, c_float, c_int, c_size_t, c_void_p, POINTER
 
+import torch  # (before the library is opened: torch's bundled libamdhip64 is loaded first, so both share one HIP runtime)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DANBO_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "libdanbo_hip.so")
 
@@ -248,7 +250,6 @@ def lib():
             raise RuntimeError(
                 f"{LIB_PATH} not found: build it with `make -C danbo-pytorch_amd/csrc` "
                 "(or __graft_entry__.build()).  There is no CPU / PyTorch fallback.")
-        import torch  # noqa: F401  (loads torch's bundled libamdhip64 first so both share one HIP runtime)
         l = ctypes.CDLL(LIB_PATH)
         for name, argtypes in SIGNATURES.items():
             fn = getattr(l, name)
@@ -256,6 +257,16 @@ def lib():
             fn.restype = RESTYPES.get(name, c_int)
         _lib = l
     return _lib
+
+
+def ptr(t):
+    """device pointer argument of a tensor (None -> NULL)"""
+    return None if t is None else c_void_p(t.data_ptr())
+
+
+def stream():
+    """the current HIP stream as the `void* stream` argument every entry point ends in"""
+    return c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 class HipError(RuntimeError):

@@ -9,17 +9,15 @@ every sample is evaluated, exactly as in the reference (core/networks/nerf.py:10
 import torch
 
 from . import hip_ops as ops
+from .render_engine import RenderEngine
 
 
-class AnerfEngine:
+class AnerfEngine(RenderEngine):
     def __init__(self, cfg, params, align, rows_per_chunk=1 << 22):
         self.cfg, self.p = cfg, params
         self.align = align.float().contiguous()
         self.rows_per_chunk = rows_per_chunk
         self._key_built = None
-
-    def _key(self):
-        return tuple((k, v.data_ptr(), v._version) for k, v in sorted(self.p.items()))
 
     def refresh(self):
         key = self._key()
@@ -173,11 +171,7 @@ class AnerfEngine:
 
     def render(self, rays_o, rays_d, skts, bones, cyls, cam_idx=None, N_samples=None, N_importance=None, chunk=4096,
                near_far=None, keep=False, **_):
-        cfg = self.cfg
-        S = N_samples or cfg["N_samples"]
-        Sf = N_importance or cfg["N_importance"]
-        B = cfg["density_scale"]
-        act = ops.density_act(cfg.get("density_act"))     # (RayCaster._engines sets it per call, as density_scale)
+        S, Sf, B, act = self._sampling(N_samples, N_importance)
         self.refresh()
         near, far = self.near_far(rays_o, rays_d, cyls, skts, 0.0, 1.0, chunk) if near_far is None else near_far
         z = ops.coarse_samples(near, far, S)
@@ -188,37 +182,12 @@ class AnerfEngine:
         raw_f = self.forward_samples(rays_o, rays_d, skts, cam_idx, z=z_fine, view=C)
         raw_all = ops.merge_samples(raw, raw_f, order)
         out = ops.composite(raw_all, z_all, rays_d, B, act=act)
-        ret = dict(rgb_map=out["rgb_map"], disp_map=out["disp_map"], acc_map=out["acc_map"], alpha=out["alpha"],
-                   T_i=out["weights"], rgb0=out0["rgb_map"], disp0=out0["disp_map"], acc0=out0["acc_map"],
-                   alpha0=out0["alpha"])
+        ret = self.frame_result(out, out0)
         if keep:
             ret.update(near=near, far=far, z_coarse=z, raw_coarse=raw, weights_coarse=out0["weights"], z_fine=z_fine,
                        z_sorted=z_all, sorted_idxs=order, raw_fine=raw_f, raw_sorted=raw_all)
         return ret
 
-    def render_two_net(self, fine, rays_o, rays_d, skts, bones, cyls, cam_idx=None, N_samples=None, N_importance=None,
-                       chunk=4096, near_far=None, keep=False, **_):
-        """single_net = False (reference raycasters.py:330-377): this engine's network on the S coarse samples, the two-network
-        pdf for the Sf importance depths, `fine` -- the fine network's engine -- on all S + Sf sorted samples, composited as
-        they are (no merge of coarse and fine raw)."""
-        cfg = self.cfg
-        S = N_samples or cfg["N_samples"]
-        Sf = N_importance or cfg["N_importance"]
-        B = cfg["density_scale"]
-        act = ops.density_act(cfg.get("density_act"))     # (RayCaster._engines sets it per call, as density_scale)
-        self.refresh()
-        fine.refresh()
-        near, far = self.near_far(rays_o, rays_d, cyls, skts, 0.0, 1.0, chunk) if near_far is None else near_far
-        z = ops.coarse_samples(near, far, S)
-        raw = self.forward_samples(rays_o, rays_d, skts, cam_idx, z=z, view=self.view_constants(rays_d, skts))
-        out0 = ops.composite(raw, z, rays_d, B, act=act)
-        z_all, z_fine, order = ops.importance_samples(z, out0["weights"], Sf, two_net=True)
-        raw_f = fine.forward_samples(rays_o, rays_d, skts, cam_idx, z=z_all, view=fine.view_constants(rays_d, skts))
-        out = ops.composite(raw_f, z_all, rays_d, B, act=act)
-        ret = dict(rgb_map=out["rgb_map"], disp_map=out["disp_map"], acc_map=out["acc_map"], alpha=out["alpha"],
-                   T_i=out["weights"], rgb0=out0["rgb_map"], disp0=out0["disp_map"], acc0=out0["acc_map"],
-                   alpha0=out0["alpha"])
-        if keep:
-            ret.update(near=near, far=far, z_coarse=z, raw_coarse=raw, weights_coarse=out0["weights"], z_fine=z_fine,
-                       z_sorted=z_all, sorted_idxs=order, raw_fine=raw_f)
-        return ret
+    def _network_pass(self, rays_o, rays_d, skts, bones, cam_idx, z, bounds, dense, lazy, tag):
+        """every sample is evaluated: no in-volume bits, no empty-space raw, nothing more to keep"""
+        return self.forward_samples(rays_o, rays_d, skts, cam_idx, z=z, view=self.view_constants(rays_d, skts)), None, None, {}

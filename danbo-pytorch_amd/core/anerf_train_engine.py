@@ -12,7 +12,8 @@ import ctypes
 import torch
 
 from . import _hip
-from .train_engine import DanboTrainEngine, _P
+from ._hip import ptr
+from .train_engine import DanboTrainEngine, unsupported_options
 
 
 def _names(net):
@@ -27,23 +28,10 @@ def _names(net):
 
 def supported(args, caster):
     """-> None if danbo_anerf_train_step covers this configuration, else the reason (the caller then uses the autograd path)"""
+    reason = unsupported_options(args, caster, 'NeRF')
+    if reason is not None:
+        return reason
     net = caster.network
-    if type(net).__name__ != 'NeRF':
-        return f'network {type(net).__name__}'
-    if args.loss_fn not in ('L1', 'MSE'):
-        return f'loss_fn {args.loss_fn}'
-    if getattr(args, 'reg_fn', None) not in (None, 'None') or getattr(args, 'weight_decay', None) is not None:
-        return 'regulariser / weight decay'
-    if getattr(args, 'finetune_light', False) or getattr(args, 'opt_pose', False):
-        return 'finetune_light / opt_pose'
-    if getattr(args, 'lindisp', False):
-        return 'lindisp'
-    if float(getattr(args, 'ray_noise_std', 0.) or 0.) != 0.:
-        return 'ray_noise_std'
-    if getattr(args, 'density_type', 'relu') != 'relu':
-        return f'density_type {args.density_type}'
-    if not getattr(args, 'single_net', True):
-        return 'single_net=False'
     if args.N_importance <= 0 or args.N_samples + args.N_importance > 256 or args.N_samples < 3:
         return 'sampling settings'
     try:
@@ -73,47 +61,15 @@ def supported(args, caster):
 
 
 class AnerfTrainEngine(DanboTrainEngine):
+    phases = 1      # the whole step is one phase: a split step leaves nothing for finish_backward()
+
     def __init__(self, args, caster, optimizer):
-        self.args, self.caster, self.opt = args, caster, optimizer
-        net = self.net = caster.network
-        dev = self.device = next(net.parameters()).device
-        if dev.type != 'cuda':
-            raise RuntimeError("the training step runs on the HIP path only: move the caster to a GPU first")
-        params = dict(net.named_parameters())
-        order = _names(net)
-        # every tensor starts on a 16-byte boundary (vector loads / k_dw16's stores)
-        self.offsets, off = {}, 0
-        for n in order:
-            off = (off + 3) // 4 * 4
-            self.offsets[n] = off
-            off += params[n].numel()
-        self.n_train = total = off
-        self.flat_p = torch.zeros(total, device=dev, dtype=torch.float32)
-        self.flat_g = torch.zeros(total, device=dev, dtype=torch.float32)
-        self.flat_m = torch.zeros(total, device=dev, dtype=torch.float32)
-        self.flat_v = torch.zeros(total, device=dev, dtype=torch.float32)
-        self.params = {n: params[n] for n in order}
-        with torch.no_grad():
-            for n, p in self.params.items():
-                o, k = self.offsets[n], p.numel()
-                self.flat_p[o:o + k].copy_(p.detach().reshape(-1))
-                p.data = self.flat_p[o:o + k].view(p.shape)
-                p.grad = self.flat_g[o:o + k].view(p.shape)
-        self.trainable = list(order)
-        self._adopt_optimizer_state()
-        self.t = self._optimizer_step_count()
-        self._buffers = {}
-        self._ws = None
-        self._rng_state, self._rng_seed = None, None
-        self._model_struct = None
-        self.graph = None
-        self.outputs_static = False
-        self.generation = 0
-        self.use_graph = True
-        self.fixed_draws = None
+        order = _names(caster.network)
+        self._init_flat(args, caster, optimizer, order, order, [])
+        self._init_state()
         # tau as a DEVICE scalar at a fixed address: update_tau REPLACES the module's buffer every step (core/cutoff_embedder.py) and a
         # captured graph holds pointers -- forward_backward copies the current value in front of every step
-        self._tau = torch.zeros(1, device=dev, dtype=torch.float32)
+        self._tau = torch.zeros(1, device=self.device, dtype=torch.float32)
 
     def _model(self):
         if self._model_struct is not None:
@@ -158,9 +114,7 @@ class AnerfTrainEngine(DanboTrainEngine):
         return _hip.lib().danbo_anerf_train_workspace(ctypes.byref(m), R, G, S, Sf, chunk)
 
     def _c_step(self, m, bt, o, phase, stream):
-        if phase == 2:          # a "split" step (data-parallel training): the whole step is phase 1, nothing is left for phase 2
-            return
-        _hip.check(_hip.lib().danbo_anerf_train_step(ctypes.byref(m), ctypes.byref(bt), ctypes.byref(o), _P(self._ws), self._ws.numel(), stream),
+        _hip.check(_hip.lib().danbo_anerf_train_step(ctypes.byref(m), ctypes.byref(bt), ctypes.byref(o), ptr(self._ws), self._ws.numel(), stream),
                    "danbo_anerf_train_step")
 
     def forward_backward(self, *a, **k):
@@ -182,6 +136,6 @@ class AnerfTrainEngine(DanboTrainEngine):
     def workspace_view(self, R, G, S, Sf):
         """device views of the last step's sampling decisions (z_coarse [R,S], z_fine [R,Sf], z_sorted, order [R,S+Sf])"""
         v = _hip.DanboTrainView()
-        _hip.check(_hip.lib().danbo_anerf_train_workspace_view(ctypes.byref(self._model()), R, G, S, Sf, R, _P(self._ws), ctypes.byref(v)),
+        _hip.check(_hip.lib().danbo_anerf_train_workspace_view(ctypes.byref(self._model()), R, G, S, Sf, R, ptr(self._ws), ctypes.byref(v)),
                    "danbo_anerf_train_workspace_view")
         return v

@@ -34,10 +34,7 @@ import torch
 
 from . import _hip
 from . import hip_ops as ops
-
-
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
+from ._hip import ptr as _p
 
 
 # ------------------------------------------------------------------------------------------------------------------ composite
@@ -63,15 +60,9 @@ def composite_bwd(raw: torch.Tensor, z: torch.Tensor, rays_d: torch.Tensor, B: f
     a_type, a_shift = ops._act_args((density_type, softplus_shift))
     raw, z, rays_d = (ops._f32(t, n) for t, n in ((raw, "raw"), (z, "z"), (rays_d, "rays_d")))
     d_raw = torch.empty(R, S, 4, dtype=torch.float32, device=raw.device)
-    if a_type != 0:
-        _hip.check(_hip.lib().danbo_composite_bwd_lazy_act(_p(raw), None, None, _p(z), _p(rays_d), R, S, float(B),
-                                                           _p(ops._f32(noise, "noise")), _p(ops._f32(g_rgb, "g_rgb")),
-                                                           _p(ops._f32(g_acc, "g_acc")), _p(d_raw), a_type, a_shift, ops._stream()),
-                   "danbo_composite_bwd_lazy_act")
-        return d_raw
-    _hip.check(_hip.lib().danbo_composite_bwd(_p(raw), _p(z), _p(rays_d), R, S, float(B), _p(ops._f32(noise, "noise")),
-                                              _p(ops._f32(g_rgb, "g_rgb")), _p(ops._f32(g_acc, "g_acc")), _p(d_raw), ops._stream()),
-               "danbo_composite_bwd")
+    # (no lazily filled raw here: NULL raw_empty / in-volume bits; relu through this entry is danbo_composite_bwd's kernel)
+    ops._call("danbo_composite_bwd_lazy_act", _p(raw), None, None, _p(z), _p(rays_d), R, S, float(B), _p(ops._f32(noise, "noise")),
+              _p(ops._f32(g_rgb, "g_rgb")), _p(ops._f32(g_acc, "g_acc")), _p(d_raw), a_type, a_shift, ops._stream())
     return d_raw
 
 

@@ -9,6 +9,7 @@ import ctypes
 import torch
 
 from . import _hip
+from ._hip import ptr as _p, stream as _stream  # noqa: F401  (the names the wrappers and the tests use)
 
 J = 24
 VOL = 240
@@ -19,14 +20,6 @@ MLP_PACKED_FLOATS = 659456
 VIEW_W = 128
 
 
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _f32(t, name):
     if t is None:
         return None
@@ -35,6 +28,11 @@ def _f32(t, name):
     if t.dtype != torch.float32:
         t = t.float()
     return t.contiguous()
+
+
+def cam_index(cam_idx):
+    """per-ray camera / frame-code indices as the kernels read them: flat, int64, contiguous (None stays None)"""
+    return None if cam_idx is None else cam_idx.reshape(-1).to(torch.int64).contiguous()
 
 
 def _ptr_array(tensors):
@@ -261,8 +259,7 @@ def view_consts(rays_d, skts, ray_mode, normalise, L_view, framecodes, mean_code
     n_codes = 0 if framecodes is None else framecodes.shape[0]
     cview = torch.empty(R, VIEW_W, device=rays_d.device, dtype=torch.float32)
     raw_empty = torch.empty(R, 4, device=rays_d.device, dtype=torch.float32) if empty_consts is not None else None
-    if cam_idx is not None:
-        cam_idx = cam_idx.reshape(-1).to(torch.int64).contiguous()
+    cam_idx = cam_index(cam_idx)
     _call("danbo_view_consts", _p(rays_d), _p(_f32(skts, "skts")), R, G, int(ray_mode), int(normalise), int(L_view),
           _p(framecodes), n_codes, Cf, _p(mean_code), _p(cam_idx), _p(wrt), _p(views_b), _p(rgb_w), _p(rgb_b),
           _p(empty_consts), int(rgb_order), _p(code_table), _p(ray_list), _p(ray_count), _p(cview), _p(raw_empty), _stream())
@@ -343,6 +340,23 @@ def _act_args(act):
     return _ACT_TYPES[kind], float(shift)
 
 
+def _ray_outputs(R, S, Sf, dev, flat=None, want_weights=True, merged=False):
+    """the per-ray outputs of a composite over n = S (merged: S + Sf) samples: dict(rgb_map [R,3], disp_map [R], acc_map [R],
+    weights [R,n] or None, alpha [R,n]) -- fresh, or (flat: flat_rays()'s result) its buffers of that composite"""
+    n = S + Sf if merged else S
+    if flat is not None:
+        out = dict(flat["out" if merged else "out0"])
+        assert out["alpha"].shape == (R, n)
+        return out
+    f = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)  # noqa: E731
+    return dict(rgb_map=f(R, 3), disp_map=f(R), acc_map=f(R), weights=f(R, n) if want_weights else None, alpha=f(R, n))
+
+
+def _ray_list(flat):
+    """(ray_list, ray_count) arguments: flat_rays()'s list of the rays that are not rays of constants, or none"""
+    return (None, None) if flat is None else (_p(flat["ray_list"]), _p(flat["ray_count"]))
+
+
 def composite(raw, z, rays_d, B=1.0, noise=None, bits=None, raw_empty=None, flat=None, act=None):
     """bits / raw_empty: un-filled raw (samples with in-volume word 0 take raw_empty[ray]: danbo_hip.h);
     flat: flat_rays(want_weights=True)'s result -- only its listed rays are composited, into its buffers;
@@ -351,53 +365,26 @@ def composite(raw, z, rays_d, B=1.0, noise=None, bits=None, raw_empty=None, flat
     assert a_type == 0 or flat is None, "rays of constants (flat=) do not exist under softplus"
     raw, z, rays_d = _f32(raw, "raw"), _f32(z, "z"), _f32(rays_d, "rays_d")
     R, S = z.shape
-    dev = raw.device
-    if flat is not None:
-        o0 = flat["out0"]
-        rgb, disp, acc, w, al = o0["rgb_map"], o0["disp_map"], o0["acc_map"], o0["weights"], o0["alpha"]
-        assert w is not None and w.shape == (R, S) and al.shape == (R, S)
-    else:
-        rgb = torch.empty(R, 3, device=dev, dtype=torch.float32)
-        disp = torch.empty(R, device=dev, dtype=torch.float32)
-        acc = torch.empty(R, device=dev, dtype=torch.float32)
-        w = torch.empty(R, S, device=dev, dtype=torch.float32)
-        al = torch.empty(R, S, device=dev, dtype=torch.float32)
-    if a_type != 0:
-        _call("danbo_composite_rays_fwd_act", _p(raw), _p(_f32(raw_empty, "raw_empty")), _p(bits), _p(z), _p(rays_d), R, S, float(B),
-              _p(_f32(noise, "noise")), _p(rgb), _p(disp), _p(acc), _p(w), _p(al), None, None, a_type, a_shift, _stream())
-    elif flat is not None or bits is not None:
-        _call("danbo_composite_rays_fwd", _p(raw), _p(_f32(raw_empty, "raw_empty")), _p(bits), _p(z), _p(rays_d), R, S, float(B),
-              _p(_f32(noise, "noise")), _p(rgb), _p(disp), _p(acc), _p(w), _p(al), _p(flat["ray_list"] if flat else None),
-              _p(flat["ray_count"] if flat else None), _stream())
-    else:
-        _call("danbo_composite_fwd", _p(raw), _p(z), _p(rays_d), R, S, float(B), _p(_f32(noise, "noise")),
-              _p(rgb), _p(disp), _p(acc), _p(w), _p(al), _stream())
-    return dict(rgb_map=rgb, disp_map=disp, acc_map=acc, weights=w, alpha=al)
+    out = _ray_outputs(R, S, 0, raw.device, flat)
+    assert out["weights"] is not None and out["weights"].shape == (R, S)
+    _call("danbo_composite_rays_fwd_act", _p(raw), _p(_f32(raw_empty, "raw_empty")), _p(bits), _p(z), _p(rays_d), R, S, float(B),
+          _p(_f32(noise, "noise")), _p(out["rgb_map"]), _p(out["disp_map"]), _p(out["acc_map"]), _p(out["weights"]), _p(out["alpha"]),
+          *_ray_list(flat), a_type, a_shift, _stream())
+    return out
 
 
 def importance_samples(z, weights, Sf, u=None, flat=None, two_net=False):
     """flat: flat_rays()'s result (64 < S <= 256, Sf <= 64) -- only its listed rays are resampled, into its z_fine (the rows of
     the other rays are there; their z_sorted / sorted_idx rows are never made).
-    two_net: the pdf of a caster with a separate fine network (isample_from_lineseg(is_only=False), danbo_importance_samples_pdf)"""
+    two_net: the pdf of a caster with a separate fine network (isample_from_lineseg(is_only=False))"""
     R, S = z.shape
     dev = z.device
     zs = torch.empty(R, S + Sf, device=dev, dtype=torch.float32)
     idx = torch.empty(R, S + Sf, device=dev, dtype=torch.int32)
-    if two_net:
-        zf = flat["z_fine"] if flat is not None else torch.empty(R, Sf, device=dev, dtype=torch.float32)
-        assert zf.shape == (R, Sf)
-        _call("danbo_importance_samples_pdf", _p(_f32(z, "z")), _p(_f32(weights, "weights")), R, S, Sf, _p(_f32(u, "u")), 1,
-              _p(zf), _p(zs), _p(idx), _p(flat["ray_list"] if flat else None), _p(flat["ray_count"] if flat else None), _stream())
-        return zs, zf, idx
-    if flat is not None:
-        zf = flat["z_fine"]
-        assert zf.shape == (R, Sf)
-        _call("danbo_importance_samples_rays", _p(_f32(z, "z")), _p(_f32(weights, "weights")), R, S, Sf, _p(_f32(u, "u")),
-              _p(zf), _p(zs), _p(idx), _p(flat["ray_list"]), _p(flat["ray_count"]), _stream())
-        return zs, zf, idx
-    zf = torch.empty(R, Sf, device=dev, dtype=torch.float32)
-    _call("danbo_importance_samples", _p(_f32(z, "z")), _p(_f32(weights, "weights")), R, S, Sf, _p(_f32(u, "u")),
-          _p(zf), _p(zs), _p(idx), _stream())
+    zf = flat["z_fine"] if flat is not None else torch.empty(R, Sf, device=dev, dtype=torch.float32)
+    assert zf.shape == (R, Sf)
+    _call("danbo_importance_samples_pdf", _p(_f32(z, "z")), _p(_f32(weights, "weights")), R, S, Sf, _p(_f32(u, "u")),
+          int(bool(two_net)), _p(zf), _p(zs), _p(idx), *_ray_list(flat), _stream())
     return zs, zf, idx
 
 
@@ -411,10 +398,9 @@ def flat_rays(t_lo, ray_flat, S, Sf, want_weights=False, rows_later=False, cnt=N
     t_lo = _f32(t_lo, "t_lo").reshape(-1)
     R, dev = t_lo.shape[0], t_lo.device
     assert ray_flat.dtype == torch.int32 and ray_flat.shape[0] == R
-    f = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)  # noqa: E731
-    out0 = dict(rgb_map=f(R, 3), disp_map=f(R), acc_map=f(R), weights=f(R, S) if want_weights else None, alpha=f(R, S))
-    out = dict(rgb_map=f(R, 3), disp_map=f(R), acc_map=f(R), weights=f(R, S + Sf), alpha=f(R, S + Sf))
-    zf = f(R, Sf)
+    out0 = _ray_outputs(R, S, Sf, dev, want_weights=want_weights)
+    out = _ray_outputs(R, S, Sf, dev, merged=True)
+    zf = torch.empty(R, Sf, device=dev, dtype=torch.float32)
     lst = torch.empty(R, device=dev, dtype=torch.int32)
     if cnt is None:          # (render() hands over a zeroed word of the buffer it fills once per frame)
         cnt = torch.zeros(1, device=dev, dtype=torch.int32)
@@ -436,36 +422,23 @@ def composite_importance(raw, z, rays_d, Sf, B=1.0, noise=None, u=None, bits=Non
     (out0 dict, z_sorted, z_fine, sorted_idx); bits/raw_empty: un-filled raw (see danbo_hip.h).
     flat: flat_rays()'s result -- only its listed rays are composited, into its buffers (the rows of the other rays are already
     there; their z_sorted / sorted_idx rows are never made).
-    two_net: resample with the two-network pdf (danbo_composite_importance_pdf_fwd).
+    two_net: resample with the two-network pdf (pdf 1 of the entry point; 0: the single-network pdf).
     act: the density activation (density_act; default relu); flat must be None under softplus."""
     a_type, a_shift = _act_args(act)
     assert a_type == 0 or flat is None, "rays of constants (flat=) do not exist under softplus"
     raw, z, rays_d = _f32(raw, "raw"), _f32(z, "z"), _f32(rays_d, "rays_d")
     R, S = z.shape
     dev = raw.device
-    if flat is not None:
-        o0, zf = flat["out0"], flat["z_fine"]
-        rgb, disp, acc, w, al = o0["rgb_map"], o0["disp_map"], o0["acc_map"], o0["weights"], o0["alpha"]
-        assert al.shape == (R, S) and zf.shape == (R, Sf)
-    else:
-        rgb = torch.empty(R, 3, device=dev, dtype=torch.float32)
-        disp = torch.empty(R, device=dev, dtype=torch.float32)
-        acc = torch.empty(R, device=dev, dtype=torch.float32)
-        w = torch.empty(R, S, device=dev, dtype=torch.float32) if want_weights else None
-        al = torch.empty(R, S, device=dev, dtype=torch.float32)
-        zf = torch.empty(R, Sf, device=dev, dtype=torch.float32)
+    out0 = _ray_outputs(R, S, Sf, dev, flat, want_weights)
+    zf = flat["z_fine"] if flat is not None else torch.empty(R, Sf, device=dev, dtype=torch.float32)
+    assert zf.shape == (R, Sf)
     zs = torch.empty(R, S + Sf, device=dev, dtype=torch.float32)
     idx = torch.empty(R, S + Sf, device=dev, dtype=torch.int32)
-    if a_type != 0:
-        _call("danbo_composite_importance_pdf_fwd_act", _p(raw), _p(_f32(raw_empty, "raw_empty")), _p(bits), _p(z), _p(rays_d), R, S,
-              int(Sf), float(B), _p(_f32(noise, "noise")), _p(_f32(u, "u")), int(bool(two_net)), _p(rgb), _p(disp), _p(acc), _p(w),
-              _p(al), _p(zf), _p(zs), _p(idx), None, None, a_type, a_shift, _stream())
-        return dict(rgb_map=rgb, disp_map=disp, acc_map=acc, weights=w, alpha=al), zs, zf, idx
-    # (pdf 0 runs exactly the kernels of danbo_composite_importance_fwd)
-    _call("danbo_composite_importance_pdf_fwd", _p(raw), _p(_f32(raw_empty, "raw_empty")), _p(bits), _p(z), _p(rays_d), R, S,
-          int(Sf), float(B), _p(_f32(noise, "noise")), _p(_f32(u, "u")), int(bool(two_net)), _p(rgb), _p(disp), _p(acc), _p(w), _p(al),
-          _p(zf), _p(zs), _p(idx), _p(flat["ray_list"] if flat else None), _p(flat["ray_count"] if flat else None), _stream())
-    return dict(rgb_map=rgb, disp_map=disp, acc_map=acc, weights=w, alpha=al), zs, zf, idx
+    _call("danbo_composite_importance_pdf_fwd_act", _p(raw), _p(_f32(raw_empty, "raw_empty")), _p(bits), _p(z), _p(rays_d), R, S,
+          int(Sf), float(B), _p(_f32(noise, "noise")), _p(_f32(u, "u")), int(bool(two_net)), _p(out0["rgb_map"]), _p(out0["disp_map"]),
+          _p(out0["acc_map"]), _p(out0["weights"]), _p(out0["alpha"]), _p(zf), _p(zs), _p(idx), *_ray_list(flat), a_type, a_shift,
+          _stream())
+    return out0, zs, zf, idx
 
 
 def composite_merged(raw_a, raw_b, idx, z_sorted, rays_d, B=1.0, noise=None, bits_a=None, bits_b=None, raw_empty=None,
@@ -477,29 +450,13 @@ def composite_merged(raw_a, raw_b, idx, z_sorted, rays_d, B=1.0, noise=None, bit
     raw_a, raw_b, rays_d = _f32(raw_a, "raw_a"), _f32(raw_b, "raw_b"), _f32(rays_d, "rays_d")
     R, S = raw_a.shape[:2]
     Sf = raw_b.shape[1]
-    dev = raw_a.device
-    if flat is not None:
-        assert not want_raw
-        o = flat["out"]
-        rgb, disp, acc, w, al = o["rgb_map"], o["disp_map"], o["acc_map"], o["weights"], o["alpha"]
-        assert al.shape == (R, S + Sf)
-    else:
-        rgb = torch.empty(R, 3, device=dev, dtype=torch.float32)
-        disp = torch.empty(R, device=dev, dtype=torch.float32)
-        acc = torch.empty(R, device=dev, dtype=torch.float32)
-        w = torch.empty(R, S + Sf, device=dev, dtype=torch.float32)
-        al = torch.empty(R, S + Sf, device=dev, dtype=torch.float32)
-    rs = torch.empty(R, S + Sf, 4, device=dev, dtype=torch.float32) if want_raw else None
-    if a_type != 0:
-        _call("danbo_composite_merged_fwd_act", _p(raw_a), _p(raw_b), _p(_f32(raw_empty, "raw_empty")), _p(bits_a), _p(bits_b),
-              _p(idx), _p(_f32(z_sorted, "z_sorted")), _p(rays_d), R, S, Sf, float(B), _p(_f32(noise, "noise")), _p(rgb),
-              _p(disp), _p(acc), _p(w), _p(al), _p(rs), None, None, a_type, a_shift, _stream())
-    else:
-        _call("danbo_composite_merged_fwd", _p(raw_a), _p(raw_b), _p(_f32(raw_empty, "raw_empty")), _p(bits_a), _p(bits_b),
-              _p(idx), _p(_f32(z_sorted, "z_sorted")), _p(rays_d), R, S, Sf, float(B), _p(_f32(noise, "noise")), _p(rgb),
-              _p(disp), _p(acc), _p(w), _p(al), _p(rs), _p(flat["ray_list"] if flat else None),
-              _p(flat["ray_count"] if flat else None), _stream())
-    out = dict(rgb_map=rgb, disp_map=disp, acc_map=acc, weights=w, alpha=al)
+    assert flat is None or not want_raw
+    out = _ray_outputs(R, S, Sf, raw_a.device, flat, merged=True)
+    rs = torch.empty(R, S + Sf, 4, device=raw_a.device, dtype=torch.float32) if want_raw else None
+    _call("danbo_composite_merged_fwd_act", _p(raw_a), _p(raw_b), _p(_f32(raw_empty, "raw_empty")), _p(bits_a), _p(bits_b),
+          _p(idx), _p(_f32(z_sorted, "z_sorted")), _p(rays_d), R, S, Sf, float(B), _p(_f32(noise, "noise")), _p(out["rgb_map"]),
+          _p(out["disp_map"]), _p(out["acc_map"]), _p(out["weights"]), _p(out["alpha"]), _p(rs), *_ray_list(flat), a_type, a_shift,
+          _stream())
     if want_raw:
         out["raw_sorted"] = rs
     return out
@@ -557,26 +514,26 @@ def merge_samples(a, b, idx):
 
 
 # -------------------------------------------------------------------------------------- A-NeRF
+def _anerf_grid(rays_o, rays_d, skts, z, pts, nrows, width, out):
+    """the shared front of the two A-NeRF encoders: the R x S sample grid as points (pts [R,S,3]) or as rays + depths (z [R,S]),
+    and the two outputs [nrows, width], [nrows, 24] -- fresh, or the first rows of `out`'s two buffers
+    -> ((rays_o, rays_d, z, pts): fp32 or None, skts, R, S, first output, w)"""
+    skts = _f32(skts, "skts")
+    if pts is not None:
+        geo = (None, None, None, _f32(pts, "pts"))
+    else:
+        geo = (_f32(rays_o, "rays_o"), _f32(rays_d, "rays_d"), _f32(z, "z"), None)
+    grid = geo[3] if pts is not None else geo[2]
+    if out is None:
+        out = (torch.empty(nrows, width, device=grid.device, dtype=torch.float32),
+               torch.empty(nrows, J, device=grid.device, dtype=torch.float32))
+    return geo, skts, grid.shape[0], grid.shape[1], out[0][:nrows], out[1][:nrows]
+
+
 def anerf_encode(rays_o, rays_d, skts, align, cutoff, tau, L, row0, nrows, z=None, pts=None, out=None):
     """-> x0 [nrows, (1+2L)*24+72], w [nrows,24] for samples [row0, row0+nrows) of the R x S grid."""
-    skts = _f32(skts, "skts")
-    G = skts.shape[0]
-    if pts is not None:
-        pts = _f32(pts, "pts")
-        R, S = pts.shape[0], pts.shape[1]
-        dev = pts.device
-        rays_o = rays_d = z = None
-    else:
-        rays_o, rays_d, z = _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d"), _f32(z, "z")
-        R, S = z.shape
-        dev = z.device
-    in_ch = (1 + 2 * L) * J + 3 * J
-    if out is None:
-        x0 = torch.empty(nrows, in_ch, device=dev, dtype=torch.float32)
-        w = torch.empty(nrows, J, device=dev, dtype=torch.float32)
-    else:
-        x0, w = out[0][:nrows], out[1][:nrows]
-    _call("danbo_anerf_encode_fwd", _p(rays_o), _p(rays_d), _p(z), _p(pts), R, S, G, _p(skts), _p(_f32(align, "align")),
+    geo, skts, R, S, x0, w = _anerf_grid(rays_o, rays_d, skts, z, pts, nrows, (1 + 2 * L) * J + 3 * J, out)
+    _call("danbo_anerf_encode_fwd", *map(_p, geo), R, S, skts.shape[0], _p(skts), _p(_f32(align, "align")),
           _p(_f32(cutoff, "cutoff")), float(tau), int(L), int(row0), int(nrows), _p(x0), _p(w), _stream())
     return x0, w
 
@@ -588,23 +545,8 @@ LINEAR16_ENC_K = 448       # k-slots of the recomputed density inputs (14 k-step
 def anerf_encode_compact(rays_o, rays_d, skts, align, cutoff, tau, row0, nrows, z=None, pts=None, out=None):
     """-> table [nrows, 144] (per joint (cutoff - distance, shifted distance, cutoff weight, direction x), then the 24 (direction y, z)
     pairs), w [nrows, 24]: what linear16_enc recomputes the 24 (1 + 2 L) + 72 density inputs from (576 instead of 1 728 B per sample)"""
-    skts = _f32(skts, "skts")
-    G = skts.shape[0]
-    if pts is not None:
-        pts = _f32(pts, "pts")
-        R, S = pts.shape[0], pts.shape[1]
-        dev = pts.device
-        rays_o = rays_d = z = None
-    else:
-        rays_o, rays_d, z = _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d"), _f32(z, "z")
-        R, S = z.shape
-        dev = z.device
-    if out is None:
-        table = torch.empty(nrows, ANERF_ENC_FLOATS, device=dev, dtype=torch.float32)
-        w = torch.empty(nrows, J, device=dev, dtype=torch.float32)
-    else:
-        table, w = out[0][:nrows], out[1][:nrows]
-    _call("danbo_anerf_encode_compact", _p(rays_o), _p(rays_d), _p(z), _p(pts), R, S, G, _p(skts), _p(_f32(align, "align")),
+    geo, skts, R, S, table, w = _anerf_grid(rays_o, rays_d, skts, z, pts, nrows, ANERF_ENC_FLOATS, out)
+    _call("danbo_anerf_encode_compact", *map(_p, geo), R, S, skts.shape[0], _p(skts), _p(_f32(align, "align")),
           _p(_f32(cutoff, "cutoff")), float(tau), int(row0), int(nrows), _p(table), _p(w), _stream())
     return table, w
 
@@ -714,10 +656,9 @@ def anerf_color(featv, w, C, table, cam_idx, ray0, nrays, S, rgb_w, rgb_b, alpha
     slices of one wider buffer."""
     VW = featv.shape[1]
     R_total = C.shape[1]
-    if cam_idx is not None:
-        cam_idx = cam_idx.reshape(-1).to(torch.int64).contiguous()
-        if not cam_idx.is_cuda:
-            raise RuntimeError("cam_idx: expected a CUDA/HIP tensor")
+    cam_idx = cam_index(cam_idx)
+    if cam_idx is not None and not cam_idx.is_cuda:
+        raise RuntimeError("cam_idx: expected a CUDA/HIP tensor")
     featv, ldf = _rows(featv, "featv")
     alpha, lda = _rows(alpha, "alpha")
     _call("danbo_anerf_color_fwd", _p(featv), ldf, _p(_f32(w, "w")), _p(_f32(C, "C")), _p(_f32(table, "table")),
@@ -734,8 +675,7 @@ def linear16_color(h, packed, shape, bias, w, C, table, cam_idx, ray0, S, rgb_w,
     if not isinstance(h, FragBuffer) or h.C != K1 or K2:
         raise ValueError("linear16_color: h must be the FragBuffer the layer was packed for")
     VW, M = N - 1, h.M
-    if cam_idx is not None:
-        cam_idx = cam_idx.reshape(-1).to(torch.int64).contiguous()
+    cam_idx = cam_index(cam_idx)
     _call("danbo_linear16_fwd_color", _p(h.data), K1, _p(packed), _p(_f32(bias, "bias")), VW, M, _p(_f32(w, "w")), _p(_f32(C, "C")),
           _p(_f32(table, "table")), _p(cam_idx), table.shape[0] - 1, C.shape[1], int(ray0), int(S), _p(_f32(rgb_w, "rgb_w")),
           _p(_f32(rgb_b, "rgb_b")), _p(raw_out), _stream())
@@ -835,6 +775,17 @@ def _aligned_rows(t, name):
     return buf[:, :K], buf.stride(0)
 
 
+def _linear16_out(out, M, N, device):
+    """row-order `out` of linear16 -> (the tensor to return, the matrix the kernel writes, its row stride); None: a fresh [M, N]
+    whose rows are padded to 16 bytes"""
+    if out is None:
+        out = torch.empty(M, (N + 3) // 4 * 4, device=device, dtype=torch.float32)[:, :N]
+    y, ldy = _rows(out, "out")
+    if y.data_ptr() != out.data_ptr() or tuple(y.shape) != (M, N) or ldy % 4 or y.data_ptr() % 16:
+        raise ValueError("linear16: out must be a [M, N] float32 matrix, unit column stride, rows 16-byte aligned")
+    return out, y, ldy
+
+
 def linear16(x1, packed, shape, bias=None, relu=False, x2=None, out=None, count=None):
     """y = act([x1 | x2] W^T + bias) for the rows of x1 (/ x2); `out` may be a column slice of a wider buffer whose row
     stride is a multiple of 4 floats.  x1 / x2 / out may be FragBuffers (the layer must have been packed with the matching
@@ -853,11 +804,7 @@ def linear16(x1, packed, shape, bias=None, relu=False, x2=None, out=None, count=
         if tuple(x2.shape) != (M, K2):
             raise ValueError("linear16: x2 shape")
         x2, ld2 = _aligned_rows(x2, "x2")
-    if out is None:
-        out = torch.empty(M, (N + 3) // 4 * 4, device=x1.device, dtype=torch.float32)[:, :N]
-    y, ldy = _rows(out, "out")
-    if y.data_ptr() != out.data_ptr() or tuple(y.shape) != (M, N) or ldy % 4 or y.data_ptr() % 16:
-        raise ValueError("linear16: out must be a [M, N] float32 matrix, unit column stride, rows 16-byte aligned")
+    out, y, ldy = _linear16_out(out, M, N, x1.device)
     _call("danbo_linear16_fwd", _p(x1), ld1, K1, _p(x2), ld2, K2, _p(packed), _p(_f32(bias, "bias")), N, 1 if relu else 0,
           _p(y), ldy, M, _p(count), _stream())
     return out
@@ -890,11 +837,7 @@ def _linear16_frag(x1, packed, shape, bias, relu, x2, out, count, fr):
             raise ValueError("linear16: fragment-order out does not match [rows, N]")
         y, ldy = out.data, 0
     else:
-        if out is None:
-            out = torch.empty(M, (N + 3) // 4 * 4, device=a1.device, dtype=torch.float32)[:, :N]
-        y, ldy = _rows(out, "out")
-        if y.data_ptr() != out.data_ptr() or tuple(y.shape) != (M, N) or ldy % 4 or y.data_ptr() % 16:
-            raise ValueError("linear16: out must be a [M, N] float32 matrix, unit column stride, rows 16-byte aligned")
+        out, y, ldy = _linear16_out(out, M, N, a1.device)
     _call("danbo_linear16_fwd_frag", _p(a1), ld1, K1, _p(a2), ld2, K2, _p(packed), _p(_f32(bias, "bias")), N, 1 if relu else 0,
           _p(y), ldy, M, _p(count), fr, _stream())
     return out

@@ -17,7 +17,7 @@ import torch.nn.functional as F
 
 from . import hip_ops as ops
 from .encoders import get_pe_embedder, get_pts_embedder
-from .render_engine import DanboEngine
+from .render_engine import DanboEngine, RenderEngine
 from .networks import create_nerf
 from .utils.skeleton_utils import SMPLSkeleton, bone_align_transforms, get_skel_profile_from_rest_pose
 
@@ -383,9 +383,7 @@ class RayCaster(nn.Module):
         if self.two_net:
             raw_f, enc_f = net(z_all, self.network_fine)
             out = self.network_fine.raw2outputs(raw_f, z_all, rays_d, raw_noise_std=raw_noise_std, B=B, act_fn=act_fn)
-            ret = dict(rgb_map=out['rgb_map'], disp_map=out['disp_map'], acc_map=out['acc_map'], alpha=out['alpha'],
-                       T_i=out['weights'], rgb0=out0['rgb_map'], disp0=out0['disp_map'], acc0=out0['acc_map'],
-                       alpha0=out0['alpha'])
+            ret = RenderEngine.frame_result(out, out0)
             if 'confd' in enc_f:
                 ret.update(confd=enc_f['confd'], part_invalid=enc_f['part_invalid'])
                 if 'p_valid' in enc_f:
@@ -396,9 +394,7 @@ class RayCaster(nn.Module):
         take = lambda a, b: torch.gather(torch.cat([a, b], 1), 1, idx[..., None].expand(-1, -1, a.shape[-1]))  # noqa: E731
         raw_all = take(raw, raw_f)
         out = self.network.raw2outputs(raw_all, z_all, rays_d, raw_noise_std=raw_noise_std, B=B, act_fn=act_fn)
-        ret = dict(rgb_map=out['rgb_map'], disp_map=out['disp_map'], acc_map=out['acc_map'], alpha=out['alpha'],
-                   T_i=out['weights'], rgb0=out0['rgb_map'], disp0=out0['disp_map'], acc0=out0['acc_map'],
-                   alpha0=out0['alpha'])
+        ret = RenderEngine.frame_result(out, out0)
         if 'confd' in enc:   # DANBO: the assignment logits feed the soft-softmax loss (reference :710-716)
             ret.update(confd=take(enc['confd'], enc_f['confd']), part_invalid=take(enc['part_invalid'], enc_f['part_invalid']))
             if 'p_valid' in enc and 'p_valid' in enc_f:      # torch.ops.danbo.assign_blend: the differentiable masked probabilities

@@ -9,12 +9,73 @@ Stage map (reference file:line in include/danbo_hip.h):
     pose_volumes -> [near/far -> coarse z] -> K1a cull+compact -> K1b+K2 gather/assign/blend
     -> view consts + raw fill -> K3 PE+MLP (scatter) -> K4 composite -> importance -> fine pass
 """
+import ctypes
+
 import torch
 
+from . import _hip
 from . import hip_ops as ops
 
 
-class DanboEngine:
+class RenderEngine:
+    """What the DANBO and the A-NeRF render engine share: the key of their packed buffers, a call's sampling settings, the result
+    dict of a two-pass render, and the render with a separate fine network, written against `_network_pass`."""
+    fuse_resample = False        # coarse composite + importance resampling in ONE launch when S, Sf <= 64
+
+    def _key(self):
+        return tuple((k, v.data_ptr(), v._version) for k, v in sorted(self.p.items()))
+
+    def _sampling(self, N_samples, N_importance):
+        """-> (S, Sf, density scale B, density activation); the last two are set per call by RayCaster._engines"""
+        cfg = self.cfg
+        return (N_samples or cfg["N_samples"], N_importance or cfg["N_importance"], cfg["density_scale"],
+                ops.density_act(cfg.get("density_act")))
+
+    @staticmethod
+    def frame_result(out, out0):
+        """what a two-pass render returns (reference raycasters.py:379-396): final composite `out`, coarse composite `out0`"""
+        return dict(rgb_map=out["rgb_map"], disp_map=out["disp_map"], acc_map=out["acc_map"], alpha=out["alpha"],
+                    T_i=out["weights"], rgb0=out0["rgb_map"], disp0=out0["disp_map"], acc0=out0["acc_map"],
+                    alpha0=out0["alpha"])
+
+    def _network_pass(self, rays_o, rays_d, skts, bones, cam_idx, z, bounds, dense, lazy, tag):
+        """this engine's network on the samples at depths z [R, n], all inside bounds = (near, far); tag: "coarse" / "fine"
+        -> (raw [R,n,4], in-volume bits or None, per-ray empty-space raw or None, extras for keep=True).  With bits, raw rows
+        whose word is 0 are unwritten: the composite reads the empty-space raw for them."""
+        raise NotImplementedError
+
+    def render_two_net(self, fine, rays_o, rays_d, skts, bones, cyls, cam_idx=None, N_samples=None, N_importance=None,
+                       chunk=4096, near_far=None, dense=False, keep=False):
+        """The hierarchical render of a caster with a separate fine network (single_net = False, reference raycasters.py:330-377):
+        this engine's network on the S coarse samples and their composite (rgb0 ...); the two-network pdf (is_only=False) for the
+        Sf importance depths; `fine` -- the fine network's engine -- on ALL S + Sf samples in sorted order, composited as they
+        are: coarse and fine raw are never merged.  The bounds are this (the coarse) engine's, as the reference's
+        use_volume_near_far.  No rays of constants here: the fine pass reads z_sorted of every ray, so every ray is resampled."""
+        S, Sf, B, act = self._sampling(N_samples, N_importance)
+        self.refresh()
+        fine.refresh()
+        lazy = not dense and not keep
+        near, far = self.near_far(rays_o, rays_d, cyls, skts, 0.0, 1.0, chunk) if near_far is None else near_far
+        z = ops.coarse_samples(near, far, S)
+        raw, bits, empty, ex = self._network_pass(rays_o, rays_d, skts, bones, cam_idx, z, (near, far), dense, lazy, "coarse")
+        if self.fuse_resample and S <= 64 and Sf <= 64:
+            out0, z_all, z_fine, order = ops.composite_importance(raw, z, rays_d, Sf, B, bits=bits, raw_empty=empty,
+                                                                  want_weights=keep, two_net=True, act=act)
+        else:
+            out0 = ops.composite(raw, z, rays_d, B, bits=bits, raw_empty=empty, act=act)
+            z_all, z_fine, order = ops.importance_samples(z, out0["weights"], Sf, two_net=True)
+        raw_f, bits_f, empty_f, ex_f = fine._network_pass(rays_o, rays_d, skts, bones, cam_idx, z_all, (near, far), dense, lazy, "fine")
+        out = ops.composite(raw_f, z_all, rays_d, B, bits=bits_f, raw_empty=empty_f, act=act)
+        ret = self.frame_result(out, out0)
+        if keep:
+            ret.update(near=near, far=far, z_coarse=z, raw_coarse=raw, weights_coarse=out0["weights"], z_fine=z_fine,
+                       z_sorted=z_all, sorted_idxs=order, raw_fine=raw_f, **ex, **ex_f)
+        return ret
+
+
+class DanboEngine(RenderEngine):
+    fuse_resample = True
+
     def __init__(self, cfg, params, align, buffers=None, mlp_mode="f16split"):
         """cfg: dict (see core/utils/synthetic.model_config); params: name -> CUDA tensor using the
         reference's state_dict names; align: [24,4,4] bone-align transforms."""
@@ -39,9 +100,6 @@ class DanboEngine:
         self.group_rows = False
 
     # ------------------------------------------------------------------ derived buffers
-    def _key(self):
-        return tuple((k, v.data_ptr(), v._version) for k, v in sorted(self.p.items()))
-
     def refresh(self):
         key = self._key()
         if key == self._packed_key and getattr(self, "_built_mode", None) == (self.mlp_mode, self.mlp_form):
@@ -249,18 +307,16 @@ class DanboEngine:
     # ------------------------------------------------------------------ the same chain behind ONE C call
     def render_frame_c(self, rays_o, rays_d, skts, bones, cyls, cam_idx=None, N_samples=None, N_importance=None, chunk=4096):
         """`render()` through `danbo_render_frame` (include/danbo_hip.h): the library enqueues the whole chain itself, out of
-        one workspace buffer -- the entry point a C host binds.  Same kernels, same order: bit-identical outputs.  Under softplus
-        (cfg["density_act"]) through `danbo_render_frame_act`, which evaluates every ray whatever flat_rays_ok says."""
-        import ctypes
-        from . import _hip
+        one workspace buffer -- the entry point a C host binds.  Same kernels, same order: bit-identical outputs.  The call is
+        `danbo_render_frame_act` (relu: the chain of `danbo_render_frame`); under softplus (cfg["density_act"]) it evaluates every
+        ray whatever flat_rays_ok says."""
         assert self.mlp_mode == "f16split" and self.mlp_form == 32
         self.refresh()
         cfg = self.cfg
-        S, Sf = N_samples or cfg["N_samples"], N_importance or cfg["N_importance"]
+        S, Sf, _, act = self._sampling(N_samples, N_importance)
         f32 = lambda t: None if t is None else t.float().contiguous()  # noqa: E731
-        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
         rays_o, rays_d, skts, bones, cyls = (f32(t) for t in (rays_o, rays_d, skts, bones, cyls))
-        cam = None if (cam_idx is None or not cfg["use_framecode"]) else cam_idx.reshape(-1).to(torch.int64).contiguous()
+        cam = ops.cam_index(cam_idx) if cfg["use_framecode"] else None
         R, G, dev = rays_o.shape[0], skts.shape[0], rays_o.device
         gw, aw = self.gw, self.aw
         m = _hip.DanboModel()
@@ -290,13 +346,8 @@ class DanboEngine:
         o = _hip.DanboFrameOut(**{k: v.data_ptr() for k, v in out.items()})
         nbytes = _hip.lib().danbo_render_frame_workspace(R, G, S, Sf, int(chunk), m.graph_width)
         ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-        a_type, a_shift = ops._act_args(cfg.get("density_act"))
-        if a_type != 0:
-            _hip.check(_hip.lib().danbo_render_frame_act(ctypes.byref(m), ctypes.byref(r), S, Sf, ctypes.byref(o), ptr(ws), nbytes,
-                                                         a_type, a_shift, ops._stream()), "danbo_render_frame_act")
-        else:
-            _hip.check(_hip.lib().danbo_render_frame(ctypes.byref(m), ctypes.byref(r), S, Sf, ctypes.byref(o), ptr(ws), nbytes,
-                                                     ops._stream()), "danbo_render_frame")
+        ops._call("danbo_render_frame_act", ctypes.byref(m), ctypes.byref(r), S, Sf, ctypes.byref(o), _hip.ptr(ws), nbytes,
+                  *ops._act_args(act), ops._stream())
         out["T_i"] = out.pop("weights")
         return out
 
@@ -310,11 +361,7 @@ class DanboEngine:
 
     def render(self, rays_o, rays_d, skts, bones, cyls, cam_idx=None, N_samples=None, N_importance=None,
                chunk=4096, near_far=None, dense=False, keep=False):
-        cfg = self.cfg
-        S = N_samples or cfg["N_samples"]
-        Sf = N_importance or cfg["N_importance"]
-        B = cfg["density_scale"]
-        act = ops.density_act(cfg.get("density_act"))     # (RayCaster._engines sets it per call, as density_scale)
+        S, Sf, B, act = self._sampling(N_samples, N_importance)
         self.refresh()
         fused = S <= 64 and Sf <= 64
         lazy = not dense and not keep      # skip the raw pre-fill: consumers read raw_empty where bits == 0
@@ -361,61 +408,22 @@ class DanboEngine:
         out = ops.composite_merged(raw, raw_f, order, z_all, rays_d, B, bits_a=ex["valid_bits"] if lazy else None,
                                    bits_b=ex_f["valid_bits"] if lazy else None, raw_empty=view[1] if lazy else None,
                                    want_raw=keep, flat=flat, act=act)
-        raw_all = out.get("raw_sorted")
-        ret = dict(rgb_map=out["rgb_map"], disp_map=out["disp_map"], acc_map=out["acc_map"], alpha=out["alpha"],
-                   T_i=out["weights"], rgb0=out0["rgb_map"], disp0=out0["disp_map"], acc0=out0["acc_map"],
-                   alpha0=out0["alpha"])
+        ret = self.frame_result(out, out0)
         if keep:
             ret.update(near=near, far=far, z_coarse=z, raw_coarse=raw, weights_coarse=out0["weights"], z_fine=z_fine,
-                       z_sorted=z_all, sorted_idxs=order, raw_fine=raw_f, raw_sorted=raw_all,
+                       z_sorted=z_all, sorted_idxs=order, raw_fine=raw_f, raw_sorted=out.get("raw_sorted"),
                        count_coarse=ex["count"], count_fine=ex_f["count"], valid_bits=ex["valid_bits"])
         return ret
 
-    # ------------------------------------------------------------------ RayCaster.render_rays, single_net = False (eval)
-    def render_two_net(self, fine, rays_o, rays_d, skts, bones, cyls, cam_idx=None, N_samples=None, N_importance=None,
-                       chunk=4096, near_far=None, dense=False, keep=False):
-        """The hierarchical render of a caster with a separate fine network (reference raycasters.py:330-377): this engine's
-        network on the S coarse samples and their composite (rgb0 ...); the two-network pdf (is_only=False) for the Sf importance
-        depths; `fine` -- the fine network's engine -- on ALL S + Sf samples in sorted order, composited as they are: coarse and
-        fine raw are never merged.  The bounds are this (the coarse) engine's, as the reference's use_volume_near_far.
-
-        Each pass culls with its own network's volumes (the fine network's axis_scale is its own parameter: a mask from the coarse
-        boxes could drop fine samples inside a fine volume).  No rays of constants here: the fine pass reads z_sorted of every ray,
-        so every ray is resampled; lazy (dense=False, keep=False) still leaves the raw rows outside every volume unwritten, each
-        composite reading its own network's empty-space raw for them -- bit for bit the filled result."""
-        cfg = self.cfg
-        S = N_samples or cfg["N_samples"]
-        Sf = N_importance or cfg["N_importance"]
-        B = cfg["density_scale"]
-        act = ops.density_act(cfg.get("density_act"))
-        self.refresh()
-        fine.refresh()
-        lazy = not dense and not keep
-        near, far = self.near_far(rays_o, rays_d, cyls, skts, 0.0, 1.0, chunk) if near_far is None else near_far
-        z = ops.coarse_samples(near, far, S)
-        # candidate bones over [near, far] -- coarse and importance depths both lie inside -- per network
-        masks = [None if dense else ops.ray_bone_mask(rays_o, rays_d, skts, e.align, e.axis_scale, near, far) for e in (self, fine)]
-        counts = torch.zeros(2, device=rays_o.device, dtype=torch.int32)
+    # ------------------------------------------------------------------ one network pass of render_two_net (single_net = False)
+    def _network_pass(self, rays_o, rays_d, skts, bones, cam_idx, z, bounds, dense, lazy, tag):
+        """Each pass culls with its own network's volumes (the fine network's axis_scale is its own parameter: a mask from the coarse
+        boxes could drop fine samples inside a fine volume).  lazy (dense=False, keep=False) leaves the raw rows outside every
+        volume unwritten, the composite reading this network's empty-space raw for them -- bit for bit the filled result."""
+        # candidate bones over [near, far]: coarse and importance depths both lie inside
+        mask = None if dense else ops.ray_bone_mask(rays_o, rays_d, skts, self.align, self.axis_scale, *bounds)
         view = self.view_constants(rays_d, skts, cam_idx)
         raw, ex = self.forward_samples(rays_o, rays_d, skts, bones, cam_idx, z=z, dense=dense, volumes=self.volumes(bones), view=view,
-                                       fill=not lazy, ray_mask=masks[0], count=counts[0:1])
+                                       fill=not lazy, ray_mask=mask)
         bits, empty = (ex["valid_bits"], view[1]) if lazy else (None, None)
-        if S <= 64 and Sf <= 64:
-            out0, z_all, z_fine, order = ops.composite_importance(raw, z, rays_d, Sf, B, bits=bits, raw_empty=empty,
-                                                                  want_weights=keep, two_net=True, act=act)
-        else:
-            out0 = ops.composite(raw, z, rays_d, B, bits=bits, raw_empty=empty, act=act)
-            z_all, z_fine, order = ops.importance_samples(z, out0["weights"], Sf, two_net=True)
-        view_f = fine.view_constants(rays_d, skts, cam_idx)
-        raw_f, ex_f = fine.forward_samples(rays_o, rays_d, skts, bones, cam_idx, z=z_all, dense=dense, volumes=fine.volumes(bones),
-                                           view=view_f, fill=not lazy, ray_mask=masks[1], count=counts[1:2])
-        bits_f, empty_f = (ex_f["valid_bits"], view_f[1]) if lazy else (None, None)
-        out = ops.composite(raw_f, z_all, rays_d, B, bits=bits_f, raw_empty=empty_f, act=act)
-        ret = dict(rgb_map=out["rgb_map"], disp_map=out["disp_map"], acc_map=out["acc_map"], alpha=out["alpha"],
-                   T_i=out["weights"], rgb0=out0["rgb_map"], disp0=out0["disp_map"], acc0=out0["acc_map"],
-                   alpha0=out0["alpha"])
-        if keep:
-            ret.update(near=near, far=far, z_coarse=z, raw_coarse=raw, weights_coarse=out0["weights"], z_fine=z_fine,
-                       z_sorted=z_all, sorted_idxs=order, raw_fine=raw_f, count_coarse=ex["count"], count_fine=ex_f["count"],
-                       valid_bits=ex["valid_bits"], valid_bits_fine=ex_f["valid_bits"])
-        return ret
+        return raw, bits, empty, {"count_" + tag: ex["count"], "valid_bits" + ("_fine" if tag == "fine" else ""): ex["valid_bits"]}

@@ -16,15 +16,15 @@ import math
 import torch
 
 from . import _hip
+from . import hip_ops
+from ._hip import ptr
 
-_P = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
 
-
-def supported(args, caster):
-    """-> None if the fused step covers this configuration, else the reason (the caller then uses the autograd path)"""
-    net = caster.network
-    if type(net).__name__ != 'DANBO':
-        return f'network {type(net).__name__}'
+def unsupported_options(args, caster, network):
+    """what both fused steps (this one and core/anerf_train_engine.py) refuse alike: another network class than `network`, or an
+    option the C steps have no field for -> the reason, else None"""
+    if type(caster.network).__name__ != network:
+        return f'network {type(caster.network).__name__}'
     if args.loss_fn not in ('L1', 'MSE'):
         return f'loss_fn {args.loss_fn}'
     if getattr(args, 'reg_fn', None) not in (None, 'None') or getattr(args, 'weight_decay', None) is not None:
@@ -41,6 +41,15 @@ def supported(args, caster):
         return f'density_type {args.density_type}'
     if not getattr(args, 'single_net', True):
         return 'single_net=False'
+    return None
+
+
+def supported(args, caster):
+    """-> None if the fused step covers this configuration, else the reason (the caller then uses the autograd path)"""
+    reason = unsupported_options(args, caster, 'DANBO')
+    if reason is not None:
+        return reason
+    net = caster.network
     if args.agg_type != 'sigmoid' or args.N_importance <= 0 or args.N_samples + args.N_importance > 256 or args.N_samples < 3:
         return 'sampling / aggregation settings'
     if net.voxel_pe_fn.num_freqs != 6 or net.W != 256 or net.D != 8 or list(net.skips) != [4]:
@@ -86,32 +95,39 @@ def adopt_adam_state(opt, params, offsets, flat_m, flat_v):
 
 
 class DanboTrainEngine:
+    phases = 2      # of the C step: forward_backward(split=True) stops after the first, finish_backward() runs the second
+
     def __init__(self, args, caster, optimizer):
+        params = dict(caster.network.named_parameters())
+        order = [n for n in _hip.TRAIN_TENSORS if n in params]
+        order.remove('alpha_linear.bias')
+        order.insert(order.index('feature_linear.bias') + 1, 'alpha_linear.bias')
+        self._init_flat(args, caster, optimizer, order, [n for n in order if params[n].requires_grad],
+                        [n for n in order if not params[n].requires_grad])
+        self._init_state()
+
+    def _init_flat(self, args, caster, optimizer, order, trainable, frozen):
+        """the flat buffers: the tensors `trainable`, then `frozen` (together: `order`), back to back; every parameter, its .grad
+        and -- for the trainable ones -- its Adam moments become views of them"""
         self.args, self.caster, self.opt = args, caster, optimizer
         net = self.net = caster.network
         dev = self.device = next(net.parameters()).device
         if dev.type != 'cuda':
             raise RuntimeError("the training step runs on the HIP path only: move the caster to a GPU first")
         params = dict(net.named_parameters())
-        names = [n for n in _hip.TRAIN_TENSORS if n in params]
-        order = list(names)
-        order.remove('alpha_linear.bias')
-        order.insert(order.index('feature_linear.bias') + 1, 'alpha_linear.bias')
-        trainable = [n for n in order if params[n].requires_grad]
-        frozen = [n for n in order if not params[n].requires_grad]
-        # every tensor starts on a 16-byte boundary (vector loads in the kernels) except alpha_linear.bias, which must follow
-        # feature_linear.bias immediately
-        self.offsets, off = {}, 0
+        # every tensor starts on a 16-byte boundary (vector loads in the kernels, k_dw16's stores) except alpha_linear.bias where it
+        # follows feature_linear.bias: immediately, the DANBO step evaluates the two layers as one 257-wide layer
+        self.offsets, off, prev = {}, 0, None
         for n in trainable + frozen:
-            if n != 'alpha_linear.bias':
+            if not (n == 'alpha_linear.bias' and prev == 'feature_linear.bias'):
                 off = (off + 3) // 4 * 4
             self.offsets[n] = off
             off += params[n].numel()
             if n == trainable[-1]:
                 self.n_train = off
-        total = off
-        self.flat_p = torch.zeros(total, device=dev, dtype=torch.float32)
-        self.flat_g = torch.zeros(total, device=dev, dtype=torch.float32)
+            prev = n
+        self.flat_p = torch.zeros(off, device=dev, dtype=torch.float32)
+        self.flat_g = torch.zeros(off, device=dev, dtype=torch.float32)
         self.flat_m = torch.zeros(self.n_train, device=dev, dtype=torch.float32)
         self.flat_v = torch.zeros(self.n_train, device=dev, dtype=torch.float32)
         self.params = {n: params[n] for n in order}
@@ -121,14 +137,17 @@ class DanboTrainEngine:
                 self.flat_p[o:o + k].copy_(p.detach().reshape(-1))
                 p.data = self.flat_p[o:o + k].view(p.shape)
                 p.grad = self.flat_g[o:o + k].view(p.shape)
-        self.trainable = trainable
+        self.trainable = list(trainable)
+
+    def _init_state(self):
         self._adopt_optimizer_state()
         self.t = self._optimizer_step_count()
         self._buffers = {}
         self._ws = None
         self._rng_state, self._rng_seed = None, None     # danbo_random_draws' device-side state (see _rng)
         self._model_struct = None
-        self.graph = None           # (key, CUDAGraph, static inputs, outputs)
+        self.graph = None           # (key, CUDAGraph, static inputs, outputs, CUDAGraph of phase 2 or None)
+        self._pending = None        # (outputs, graph of phase 2 or None) between forward_backward(split=True) and finish_backward()
         self.outputs_static = False
         self.generation = 0         # forward_backward calls so far: a replayed graph's outputs are STATIC buffers, valid until the next call
         self.use_graph = True
@@ -164,7 +183,6 @@ class DanboTrainEngine:
         keep['adj0'] = gl[0].adj.detach().float().reshape(24, 24).contiguous()
         keep['adj1'] = gl[1].adj.detach().float().reshape(24, 24).contiguous()
         keep['adja'] = pl[0].adj.detach().float().reshape(24, 24).contiguous()
-        from . import hip_ops
         hip_ops.check_smpl_adjacency(pl[0].adj)      # the forward of the step runs k_assign16 (SMPL neighbour table compiled in)
         keep['align'] = self.caster.transforms[0].to(self.device).float().contiguous()
         keep['init_scale'] = net.graph_net.init_scale.to(self.device).float().contiguous()
@@ -240,30 +258,31 @@ class DanboTrainEngine:
         if self._ws is None or self._ws.numel() < nbytes:
             self._ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
         bt = _hip.DanboTrainBatch(
-            rays_o=_P(t['rays_o']), rays_d=_P(t['rays_d']), skts=_P(t['skts']), bones=_P(t['bones']), cyls=_P(t['cyls']),
-            near_in=_P(t.get('near_in')), far_in=_P(t.get('far_in')), cam_idx=_P(t.get('cam_idx')), target=_P(t['target']),
-            bgs=_P(t.get('bgs')), t_rand=_P(rnd.get('t_rand')), u_rand=_P(rnd.get('u_rand')), noise_c=_P(rnd.get('noise_c')),
-            noise_f=_P(rnd.get('noise_f')), R=R, G=G, S=S, Sf=Sf, chunk=chunk)
+            rays_o=ptr(t['rays_o']), rays_d=ptr(t['rays_d']), skts=ptr(t['skts']), bones=ptr(t['bones']), cyls=ptr(t['cyls']),
+            near_in=ptr(t.get('near_in')), far_in=ptr(t.get('far_in')), cam_idx=ptr(t.get('cam_idx')), target=ptr(t['target']),
+            bgs=ptr(t.get('bgs')), t_rand=ptr(rnd.get('t_rand')), u_rand=ptr(rnd.get('u_rand')), noise_c=ptr(rnd.get('noise_c')),
+            noise_f=ptr(rnd.get('noise_f')), R=R, G=G, S=S, Sf=Sf, chunk=chunk)
         if '_rng' in rnd:
             state, n_u, n_n, std = rnd['_rng']
-            bt.rng_state, bt.rng_uniform, bt.rng_normal = _P(state), _P(rnd.get('_u')), _P(rnd.get('_n'))
+            bt.rng_state, bt.rng_uniform, bt.rng_normal = ptr(state), ptr(rnd.get('_u')), ptr(rnd.get('_n'))
             bt.n_uniform, bt.n_normal, bt.normal_std = n_u, n_n, float(std)
-        o = _hip.DanboTrainOut(**{k: _P(v) for k, v in out.items()})
+        o = _hip.DanboTrainOut(**{k: ptr(v) for k, v in out.items()})
         out['_keep'] = (rnd, bt, o)
         self._step_phase(out, 1 if split else 0)
         return out
 
     def _step_phase(self, out, phase):
-        """phase 0: the whole step; 1: up to the pose-GNN adjoint (every gradient but the dense layers' final); 2: the rest"""
+        """phase 0: the whole step; 1: up to the pose-GNN adjoint (every gradient but the dense layers' final); 2: the rest.
+        A step of ONE phase (`phases`: A-NeRF) is whole for 0 and 1 alike and is never asked for 2."""
         _, bt, o = out['_keep']
-        self._c_step(self._model(), bt, o, int(phase), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        self._c_step(self._model(), bt, o, int(phase), _hip.stream())
 
     # the two C entry points of the step (core/anerf_train_engine.py overrides them with danbo_anerf_train_*)
     def _c_workspace(self, m, R, G, S, Sf, chunk):
         return _hip.lib().danbo_train_workspace(ctypes.byref(m), R, G, S, Sf, chunk)
 
     def _c_step(self, m, bt, o, phase, stream):
-        _hip.check(_hip.lib().danbo_train_step_phase(ctypes.byref(m), ctypes.byref(bt), ctypes.byref(o), _P(self._ws), self._ws.numel(),
+        _hip.check(_hip.lib().danbo_train_step_phase(ctypes.byref(m), ctypes.byref(bt), ctypes.byref(o), ptr(self._ws), self._ws.numel(),
                                                      phase, stream), "danbo_train_step")
 
     def _own_seed(self):
@@ -355,7 +374,7 @@ class DanboTrainEngine:
             return x.contiguous() if contiguous else x
         t = dict(rays_o=f(rays_o), rays_d=f(rays_d), skts=f(skts), bones=f(bones), cyls=f(cyls), target=f(target), bgs=f(bgs),
                  near_in=f(near_in), far_in=f(far_in))
-        t['cam_idx'] = None if cam_idx is None else cam_idx.reshape(-1).to(torch.int64).contiguous()
+        t['cam_idx'] = hip_ops.cam_index(cam_idx)
         return {k: v for k, v in t.items() if v is not None}
 
     def forward_backward(self, rays_o, rays_d, skts, bones, cyls, cam_idx, target, bgs, S, Sf, perturb=0., raw_noise_std=0.,
@@ -371,6 +390,7 @@ class DanboTrainEngine:
                                 near_in, far_in, contiguous=not graphed)
         if t.get('bgs') is not None and t['bgs'].numel() != t['target'].numel():
             t['bgs'] = t['bgs'].expand_as(t['target']).contiguous()
+        second = split and self.phases == 2      # a phase is left for finish_backward()
         if not graphed:
             out = self._launch(t, S, Sf, perturb, raw_noise_std, split)
             self._pending = (out, None) if split else None
@@ -395,7 +415,7 @@ class DanboTrainEngine:
             side.wait_stream(cur)
             with torch.cuda.stream(side):        # eager warm-up off the capture: lazy initialisations, workspace allocation
                 w = self._launch(static, S, Sf, perturb, raw_noise_std, split)
-                if split:
+                if second:
                     self._step_phase(w, 2)
             cur.wait_stream(side)
             # keep_graph: the captured hipGraph_t stays inspectable (raw_cuda_graph(); tests walk its edges: nothing may run beside K2)
@@ -403,7 +423,7 @@ class DanboTrainEngine:
             with torch.cuda.graph(g):
                 outs = self._launch(static, S, Sf, perturb, raw_noise_std, split)
             g2 = None
-            if split:                             # the weight-gradient GEMMs as their own graph: the all-reduce of the finished
+            if second:                            # the weight-gradient GEMMs as their own graph: the all-reduce of the finished
                 g2 = torch.cuda.CUDAGraph()       # gradients is launched between the two replays
                 with torch.cuda.graph(g2):
                     self._step_phase(outs, 2)
@@ -418,17 +438,18 @@ class DanboTrainEngine:
 
     @staticmethod
     def _gather_inputs(static, t):
-        from . import hip_ops
         hip_ops.gather_rows(static['_flat'], [(t[k], off) for k, off, _ in static['_spans']])
 
     def finish_backward(self):
         """second half of a split step (forward_backward(..., split=True)): the dense layers' weight gradients"""
         outs, g2 = self._pending
+        self._pending = None
+        if self.phases == 1:        # the one phase ran in forward_backward: nothing is left
+            return
         if g2 is not None:
             g2.replay()
         else:
             self._step_phase(outs, 2)
-        self._pending = None
 
     def grad_buckets(self):
         """(finished after phase 1, finished after phase 2): the flat gradient of the pose GNN, the assignment net and the axis
@@ -445,10 +466,9 @@ class DanboTrainEngine:
         self.t += 1
         # the step's scalars are kernel ARGUMENTS (danbo_adam_step, ABI 2): the host may run any number of steps ahead of the GPU
         # (sync_stats=False) without a later step's bias corrections reaching an earlier step's launch
-        _hip.check(_hip.lib().danbo_adam_step(_P(self.flat_p), _P(self.flat_g), _P(self.flat_m), _P(self.flat_v), self.n_train,
+        _hip.check(_hip.lib().danbo_adam_step(ptr(self.flat_p), ptr(self.flat_g), ptr(self.flat_m), ptr(self.flat_v), self.n_train,
                                               float(lr), 1.0 - b1 ** self.t, math.sqrt(1.0 - b2 ** self.t), float(grad_scale),
-                                              float(b1), float(b2), float(grp['eps']),
-                                              ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "danbo_adam_step")
+                                              float(b1), float(b2), float(grp['eps']), _hip.stream()), "danbo_adam_step")
         # torch.optim.Adam's per-parameter `step` entries (distinct CPU tensors, _adopt_optimizer_state): one fused in-place add
         torch._foreach_add_(self._step_tensors, 1.0)
         # the kernel wrote the parameters behind torch's back: bump their version counters, which the eval engine's packed weight

@@ -22,18 +22,13 @@ Gradient semantics follow the reference: `window` is detached and `invalid` is n
 (core/networks/gnn_backbone.py:802-808); sample depths are detached (core/utils/ray_utils.py:287); no gradient reaches
 pts / skts / bones (opt_pose is off).
 """
-import ctypes
-
 import torch
 import torch.nn.functional as F
 
 from . import _hip
 from . import custom_ops  # noqa: F401  (registers torch.ops.danbo.*)
 from . import hip_ops as ops
-
-
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
+from ._hip import ptr as _p
 
 
 # --------------------------------------------------------------------------------------
@@ -111,7 +106,6 @@ class Linear16Fn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        import ctypes
         x1, x2, weight, y = ctx.saved_tensors
         K1, K2 = ctx.K1, ctx.K2
         N, M = weight.shape[0], x1.shape[0]

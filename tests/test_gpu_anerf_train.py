@@ -277,6 +277,45 @@ def test_fused_anerf_step_replays_bitwise_and_trains():
     assert float(st["step"]) == 40 and st["exp_avg"].data_ptr() >= eng.flat_m.data_ptr()
 
 
+def test_split_anerf_step_is_the_whole_step_and_holds_no_second_graph():
+    """The A-NeRF step has ONE phase (AnerfTrainEngine.phases): forward_backward(split=True) + finish_backward() -- what data-parallel
+    training calls -- is the unsplit step.  Two graphed training steps (perturb = 1, raw_noise_std = 1, Adam update after each) from
+    one snapshot, split and unsplit: every output and the flat gradient of both steps bit for bit the same; no second HIP graph is
+    captured, nothing is pending after finish_backward(), and the late gradient bucket is empty (the whole gradient is final after
+    the first collective)."""
+    g = golden("anerf_train")
+    args, caster, trainer, opt, cfg, sd = build(g, perturb="1", noise="1")
+    batch = batch_of(g)
+    S, Sf = int(g["N_samples"]), int(g["N_importance"])
+    eng, _ = engine_step(trainer, batch, S, Sf, perturb=1.0, raw_noise_std=1.0)         # the random stream exists from here on
+    assert eng.phases == 1 and eng.use_graph
+    snap = eng.snapshot()
+
+    def two_steps(split):
+        eng.restore(snap)
+        seen = []
+        for _ in range(2):
+            _, out = engine_step(trainer, batch, S, Sf, perturb=1.0, raw_noise_std=1.0, split=split)
+            assert eng.outputs_static and eng.graph is not None and eng.graph[4] is None      # graphed, and ONE graph
+            if split:
+                assert eng._pending is not None and eng._pending[1] is None
+                eng.finish_backward()
+            assert eng._pending is None
+            seen.append(dict({k: v.clone() for k, v in out.items() if torch.is_tensor(v)}, flat_g=eng.flat_g.clone()))
+            eng.adam_step(1e-3)
+        return seen
+
+    whole, halves = two_steps(False), two_steps(True)
+    for a, b in zip(whole, halves):
+        assert set(a) == set(b) and {"rgb_map", "rgb0", "loss", "flat_g"} <= set(a)
+        for k in a:
+            assert torch.equal(a[k], b[k]), k
+        assert bool(torch.isfinite(a["flat_g"]).all()) and float(a["flat_g"].abs().max()) > 0
+    assert not torch.equal(whole[0]["flat_g"], whole[1]["flat_g"])                      # (the second step saw updated weights)
+    early, late = eng.grad_buckets()
+    assert late.numel() == 0 and early.data_ptr() == eng.flat_g.data_ptr() and early.numel() == eng.n_train == eng.flat_g.numel()
+
+
 def test_autograd_path_runs_on_the_same_kernels_and_agrees_with_the_fused_step():
     """`caster.train(); caster(...)` for A-NeRF (core/train_path.forward_train_anerf: Linear16Fn on stacked / sliced weights,
     AnerfViewConstsFn, AnerfColorFn) against the fused step on the same batch: predictions to 1e-5, every gradient to 2e-4 of its max
