@@ -125,6 +125,7 @@ SIGNATURES = {
     "danbo_mesh_workspace_bytes": [I, I, I],
     "danbo_mesh_count": [P, I, I, I, c_long, c_long, F, F, P, P, P],
     "danbo_mesh_extract": [P, I, I, I, c_long, c_long, F, F, P, F, F, F, F, P, I, P, I, P],
+    "danbo_mesh_normals": [P, I, I, I, c_long, c_long, F, F, P, P, I, P],
 }
 # everything else returns int (0 = ok)
 RESTYPES = {"danbo_mesh_workspace_bytes": c_size_t, "danbo_render_frame_workspace": c_size_t, "danbo_train_workspace": c_size_t,

@@ -165,6 +165,15 @@ class AnerfEngine(RenderEngine):
         return torch.cat([self.forward_samples(None, None, skts, pts=pts[a:a + netchunk], density_only=True)
                           for a in range(0, pts.shape[0], netchunk)], 0)
 
+    def colors(self, pts, dirs, skts, bones=None, cam_idx=None, netchunk=1024 * 64):
+        """Colour of arbitrary points [M,3] seen along the directions dirs [M,3] -> [M,3] float32 in [0, 1] (DanboEngine.colors)"""
+        pts, dirs = pts.reshape(-1, 1, 3), dirs.reshape(-1, 3)
+        cam = ops.cam_index(cam_idx)
+        out = [torch.sigmoid(self.forward_samples(None, dirs[a:a + netchunk].contiguous(), skts,
+                                                  None if cam is None else cam[a:a + netchunk], pts=pts[a:a + netchunk].contiguous())[:, 0, :3])
+               for a in range(0, pts.shape[0], netchunk)]
+        return torch.cat(out, 0) if out else torch.empty(0, 3, device=pts.device, dtype=torch.float32)
+
     # ------------------------------------------------------------------ RayCaster.render_rays (eval)
     def near_far(self, rays_o, rays_d, cyls, skts=None, near0=0.0, far0=1.0, chunk=4096):
         return ops.near_far_cylinder(rays_o, rays_d, cyls, near0, far0, chunk)

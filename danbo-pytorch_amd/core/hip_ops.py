@@ -844,12 +844,14 @@ def _linear16_frag(x1, packed, shape, bias, relu, x2, out, count, fr):
 
 
 # -------------------------------------------------------------------------------------- isosurface extraction
-def marching_cubes(sigma, iso, floor=float("-inf"), scale=1.0, offset=(0.0, 0.0, 0.0)):
+def marching_cubes(sigma, iso, floor=float("-inf"), scale=1.0, offset=(0.0, 0.0, 0.0), normals=False):
     """Isosurface of a density grid in device memory (danbo_mesh_count / danbo_mesh_extract; the reference's
     mcubes.marching_cubes, run_render.py:1279).  sigma [nx,ny,nz] float32 with innermost stride 1 -- the transposed view of
     RayCaster.render_mesh_density is taken as it is, nothing is copied; every value is read as max(sigma, floor); inside = value >=
     iso.  -> verts [V,3] float32 (index units * scale + offset, per axis), faces [T,3] int32, welded, in a deterministic order,
-    normals from inside to outside.  One host read (the two counts) sizes the outputs; an empty surface launches nothing more."""
+    normals from inside to outside.  One host read (the two counts) sizes the outputs; an empty surface launches nothing more.
+    normals=True: -> verts, faces, normals [V,3] float32 -- the unit normal at every vertex (danbo_mesh_normals: the normalised
+    negative gradient of the floored grid, in index space whatever scale and offset are), one more launch on the same workspace."""
     if not sigma.is_cuda:
         raise RuntimeError("sigma: expected a CUDA/HIP tensor -- libdanbo_hip has no CPU fallback")
     if sigma.dtype != torch.float32 or sigma.dim() != 3:
@@ -872,4 +874,9 @@ def marching_cubes(sigma, iso, floor=float("-inf"), scale=1.0, offset=(0.0, 0.0,
     if V > 0:
         ox, oy, oz = (float(x) for x in offset)
         _call("danbo_mesh_extract", *grid, _p(ws), float(scale), ox, oy, oz, _p(verts), V, _p(faces), T, _stream())
-    return verts, faces
+    if not normals:
+        return verts, faces
+    nrm = torch.empty(V, 3, device=sigma.device, dtype=torch.float32)
+    if V > 0:
+        _call("danbo_mesh_normals", *grid, _p(ws), _p(nrm), V, _stream())
+    return verts, faces, nrm

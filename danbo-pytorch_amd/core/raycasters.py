@@ -19,6 +19,7 @@ from . import hip_ops as ops
 from .encoders import get_pe_embedder, get_pts_embedder
 from .render_engine import DanboEngine, RenderEngine
 from .networks import create_nerf
+from .utils.evaluation_helpers import to8b
 from .utils.skeleton_utils import SMPLSkeleton, bone_align_transforms, get_skel_profile_from_rest_pose
 
 
@@ -406,24 +407,45 @@ class RayCaster(nn.Module):
         eng = self._engine(network=self.network_fine if self.two_net else None)     # the fine network, when there is one (:716-724)
         return eng.density(pts.reshape(-1, 1, 3), skts[:1], bones[:1], netchunk=int(netchunk))
 
+    @staticmethod
+    def mesh_grid(radius, res, device):
+        """the reference's grid (raycasters.py:425-429) without the root joint: float64 linspace rounded to float32, 'xy' meshgrid
+        -> [res+1, res+1, res+1, 3], entry [a, b, c] = (t[b], t[a], t[c])"""
+        t = np.linspace(-radius, radius, res + 1)
+        return torch.tensor(np.stack(np.meshgrid(t, t, t), axis=-1).astype(np.float32), device=device)
+
     @torch.no_grad()
     def render_mesh_density(self, kps, skts, bones, subject_idxs=None, radius=1.0, res=64, render_kwargs=None,
                             netchunk=1024 * 64, v=None):
-        # the reference's grid (raycasters.py:425-429): float64 linspace rounded to float32, 'xy' meshgrid, + the root joint
-        t = np.linspace(-radius, radius, res + 1)
-        grid = torch.tensor(np.stack(np.meshgrid(t, t, t), axis=-1).astype(np.float32), device=kps.device)
+        grid = self.mesh_grid(radius, res, kps.device)
         dens = self.render_pts_density(grid.reshape(-1, 3) + kps[0, 0], kps, skts, bones, netchunk)[..., :1]
         return dens.reshape(*grid.shape[:-1]).transpose(1, 0)      # x-y swapped, as the mesh extraction expects
 
     @torch.no_grad()
-    def render_mesh_surface(self, kps, skts, bones, threshold=10., res=64, return_density=False, **kwargs):
+    def render_mesh_surface(self, kps, skts, bones, threshold=10., res=64, return_density=False, normals=False, colors=False,
+                            cams=None, radius=1.0, netchunk=1024 * 64, **kwargs):
         """The density grid of render_mesh_density and its isosurface at `threshold`, as the reference's render_mesh makes it
         (run_render.py:1278-1280): marching cubes on np.maximum(raw, 0), vertices / res - .5 per axis of the returned (x-y swapped)
         array.  The grid stays on the device and is read through its transposed view.
-        -> verts [V,3] float32, faces [T,3] int32 (device tensors) [, the raw density grid]"""
-        dens = self.render_mesh_density(kps, skts, bones, res=res, **kwargs)
-        verts, faces = ops.marching_cubes(dens, float(threshold), floor=0., scale=1. / res, offset=(-.5, -.5, -.5))
-        return (verts, faces, dens) if return_density else (verts, faces)
+        normals: the unit normal of every vertex (ops.marching_cubes(normals=True): the negative gradient of the clamped grid).
+        colors: the colour of every vertex seen head-on, to8b of engine.colors at the vertex's world position along -normal (the
+        fine network when there is one, as for the density; cams: the pose's frame-code index, where the network has frame codes).
+        Entry (i, j, k) of the swapped array lies at root + (t[i], t[j], t[k]), t = linspace(-radius, radius, res + 1), so the
+        vertex v in [-0.5, 0.5]^3 lies at root + 2 radius v and an index-space normal is the world-space one.
+        -> verts [V,3] float32, faces [T,3] int32 [, normals [V,3] float32] [, colors [V,3] uint8] (device tensors) [, the raw
+        density grid]"""
+        dens = self.render_mesh_density(kps, skts, bones, res=res, radius=radius, netchunk=netchunk, **kwargs)
+        mesh = ops.marching_cubes(dens, float(threshold), floor=0., scale=1. / res, offset=(-.5, -.5, -.5), normals=normals or colors)
+        out = list(mesh[:3] if normals else mesh[:2])
+        if colors:
+            eng = self._engine(network=self.network_fine if self.two_net else None)
+            pts = kps[0, 0].float() + 2. * float(radius) * mesh[0]
+            cam = None if cams is None else cams.reshape(-1)[:1].expand(pts.shape[0])
+            col = eng.colors(pts, -mesh[2], skts[:1], bones[:1], cam_idx=cam, netchunk=int(netchunk))
+            out.append(torch.from_numpy(to8b(col.cpu().numpy())).to(col.device))
+        if return_density:
+            out.append(dens)
+        return tuple(out)
 
 
 class _GraphCache:

@@ -304,6 +304,23 @@ class DanboEngine(RenderEngine):
             out[a:a + n] = raw[..., 3:4].reshape(n, 1)
         return out
 
+    def colors(self, pts, dirs, skts, bones, cam_idx=None, netchunk=1024 * 64):
+        """Colour of arbitrary points [M,3] seen along the directions dirs [M,3] -> [M,3] float32 in [0, 1]: forward_samples on
+        pts [M,1,3] with dirs as the per-row ray directions, netchunk rows at a time as density(), the sigmoid of raw[..., :3]
+        (the colour of a mesh vertex seen head-on: RayCaster.render_mesh_surface)."""
+        self.refresh()
+        pts, dirs = pts.reshape(-1, 1, 3), dirs.reshape(-1, 3)
+        M = pts.shape[0]
+        out = torch.empty(M, 3, device=pts.device, dtype=torch.float32)
+        vols = self.volumes(bones)
+        cam = ops.cam_index(cam_idx)
+        for a in range(0, M, netchunk):
+            p, d = pts[a:a + netchunk].contiguous(), dirs[a:a + netchunk].contiguous()
+            raw, _ = self.forward_samples(torch.zeros_like(d), d, skts, bones, None if cam is None else cam[a:a + netchunk], pts=p,
+                                          volumes=vols)
+            out[a:a + p.shape[0]] = torch.sigmoid(raw[:, 0, :3])
+        return out
+
     # ------------------------------------------------------------------ the same chain behind ONE C call
     def render_frame_c(self, rays_o, rays_d, skts, bones, cyls, cam_idx=None, N_samples=None, N_importance=None, chunk=4096):
         """`render()` through `danbo_render_frame` (include/danbo_hip.h): the library enqueues the whole chain itself, out of

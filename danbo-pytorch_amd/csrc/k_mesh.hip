@@ -14,6 +14,8 @@
 //   k_mesh_vertices   one thread per point with an owned crossing edge: t, the output transform, float[V][3].
 //   k_mesh_triangles  one thread per cell with triangles: a welded vertex index is voff[chunk of the owning point] + the rank in
 //                     that point's word + the owned edges below the axis -- read from the words, not from a 3 N index array.
+//   k_mesh_normals    (danbo_mesh_normals) one thread per point with an owned crossing edge, the walk of k_mesh_vertices: the
+//                     normalised negative gradient of the floored grid at every vertex, float[V][3] (mesh_math.hpp).
 // Workspace: 4 B per grid point + 8 B per chunk (danbo_mesh_workspace_bytes).  No allocation, no synchronisation.  gfx950, wave64.
 #include "common.hpp"
 #include "mesh_math.hpp"
@@ -158,6 +160,40 @@ __global__ __launch_bounds__(MESH_CHUNK) void k_mesh_vertices(MeshGridArgs a, co
     }
 }
 
+// The normals of the vertices k_mesh_vertices writes, by the same walk: the gradient at the point (up to 6 loads) is shared by its
+// owned edges, each adds the gradient at its upper end; every load is at a fixed offset of the thread's own point, so a wavefront's
+// are coalesced along k like those of k_mesh_classify.
+__global__ __launch_bounds__(MESH_CHUNK) void k_mesh_normals(MeshGridArgs a, const uint32_t* __restrict__ words, const int* __restrict__ voff,
+                                                             float* __restrict__ normals, int cap_v) {
+    const MeshReader at{a.sigma, a.sx, a.sy, a.floor};
+    for (int chunk = blockIdx.x; chunk < a.n_chunks; chunk += gridDim.x) {
+        const int v0 = voff[chunk];
+        if (voff[chunk + 1] == v0 || v0 >= cap_v) continue;       // no vertex here, or none below the capacity
+        const uint32_t n = (uint32_t)chunk * MESH_CHUNK + threadIdx.x;
+        if (n >= a.n_pts) continue;
+        const uint32_t w = words[n];
+        const int emask = mesh_word_emask(w);
+        if (!emask) continue;
+        int i, j, k;
+        mesh_ijk(a, n, &i, &j, &k);
+        float g0[3];
+        mesh_gradient(at, a.nx, a.ny, a.nz, i, j, k, g0);
+        long v = (long)v0 + mesh_word_vrank(w);
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax) {
+            if (!((emask >> ax) & 1)) continue;
+            if (v < cap_v) {
+                float nrm[3];
+                mesh_vertex_normal(at, a.nx, a.ny, a.nz, i, j, k, ax, a.iso, g0, nrm);
+                normals[3 * v + 0] = nrm[0];
+                normals[3 * v + 1] = nrm[1];
+                normals[3 * v + 2] = nrm[2];
+            }
+            ++v;
+        }
+    }
+}
+
 __global__ __launch_bounds__(MESH_CHUNK) void k_mesh_triangles(MeshGridArgs a, const uint32_t* __restrict__ words, const int* __restrict__ voff,
                                                                const int* __restrict__ toff, int* __restrict__ tris, int cap_t) {
     __shared__ uint64_t s_case[256];
@@ -238,5 +274,18 @@ extern "C" int danbo_mesh_extract(const float* sigma, int nx, int ny, int nz, lo
                            off_z, verts, cap_v);
     if (cap_t > 0)
         hipLaunchKernelGGL(k_mesh_triangles, dim3(grid), dim3(MESH_CHUNK), 0, (hipStream_t)stream, a, words, voff, toff, tris, cap_t);
+    DANBO_LAUNCH_RET();
+}
+
+extern "C" int danbo_mesh_normals(const float* sigma, int nx, int ny, int nz, long stride_x, long stride_y, float floor, float iso,
+                                  const void* workspace, float* normals, int cap_v, void* stream) {
+    DANBO_CHECK_ARG(sigma && workspace && normals && mesh_dims_ok(nx, ny, nz, stride_x, stride_y, floor, iso) && cap_v >= 0);
+    DANBO_CHECK_ARG((uintptr_t)sigma % 4 == 0 && (uintptr_t)workspace % 4 == 0 && (uintptr_t)normals % 4 == 0);
+    const MeshGridArgs a = mesh_args(sigma, nx, ny, nz, stride_x, stride_y, floor, iso);
+    const uint32_t* words = static_cast<const uint32_t*>(workspace);
+    const int* voff = reinterpret_cast<const int*>(static_cast<const char*>(workspace) + mesh_words_bytes(a.n_pts));
+    if (cap_v > 0)
+        hipLaunchKernelGGL(k_mesh_normals, dim3(stream_grid((long)a.n_chunks * MESH_CHUNK, MESH_CHUNK)), dim3(MESH_CHUNK), 0,
+                           (hipStream_t)stream, a, words, voff, normals, cap_v);
     DANBO_LAUNCH_RET();
 }

@@ -17,6 +17,16 @@
 //   * v_out[c] = v_index[c] * scale + offset[c], evaluated as fma(t, scale, fma(p, scale, offset)): two roundings, the first of
 //     the lower end alone -- exact for scale = 1 / 2^n and a centring offset -- so that an output centred on 0 carries t with the
 //     granularity of the OUTPUT coordinate, not of p + t (scale 1, offset 0: fl(p + t), as before).
+// Vertex normals (k_mesh_normals, mesh_normals_host; tests/test_mesh_normals.py relies on them): the normalised negative gradient
+// of the floored grid, interpolated along the vertex's edge --
+//   * d(a, b) = v(b) - v(a) in fp32 with v = mesh_value, 0 where it is not finite (a NaN read as -inf, floor = -inf);
+//   * gradient at a grid point q, per axis a: 0.5f d(q - e_a, q + e_a) inside, d(q, q + e_a) on the low face, d(q - e_a, q) on the
+//     high face (every dimension is >= 2: one of them exists);
+//   * at the vertex (p, ax, t), per component: g = fma(t, g(p + e_ax) - g(p), g(p));
+//   * m = max |g_a|: where m is 0 or a component is not finite the normal is the unit vector along ax from the inside end to the
+//     outside end (+e_ax if s0 >= iso, else -e_ax); else h = g / m (IEEE division: grids near the ends of the fp32 range neither
+//     overflow nor flush), len = sqrtf((hx hx + hy hy) + hz hz), n = -h / len: from high density to low, as the triangles'
+//     orientation.  Every operation is a separately rounded fp32 one but the fma of the interpolation.
 #pragma once
 #include "sample_math.hpp"
 
@@ -40,6 +50,63 @@ DANBO_HD float mesh_edge_t(float s0, float s1, float iso) {
 // contract like norm3_torch's (t = 0 on the two axes the edge does not run along)
 DANBO_HD float mesh_coord(int p, float t, float scale, float offset) {
     return fmaf(t, scale, fmaf((float)p, scale, offset));
+}
+
+// ---- vertex normals ----
+// the floored value at a grid point, read through the grid's strides
+struct MeshReader {
+    const float* sigma;
+    long sx, sy;
+    float floor;
+    DANBO_HD float operator()(int i, int j, int k) const { return mesh_value(sigma[i * sx + j * sy + k], floor); }
+};
+
+// d(a, b) = v(b) - v(a), 0 where it is not finite
+DANBO_HD float mesh_diff(float va, float vb) {
+    const float d = sub_rn(vb, va);
+    return d - d == 0.f ? d : 0.f;
+}
+
+// one component of the gradient at the grid point (i, j, k): along the axis with the unit step (di, dj, dk), the point's index on
+// that axis q of n
+DANBO_HD float mesh_gradient_axis(const MeshReader& at, int i, int j, int k, int di, int dj, int dk, int q, int n) {
+    if (q > 0 && q + 1 < n) return mul_rn(0.5f, mesh_diff(at(i - di, j - dj, k - dk), at(i + di, j + dj, k + dk)));
+    if (q + 1 < n) return mesh_diff(at(i, j, k), at(i + di, j + dj, k + dk));
+    return mesh_diff(at(i - di, j - dj, k - dk), at(i, j, k));
+}
+
+DANBO_HD void mesh_gradient(const MeshReader& at, int nx, int ny, int nz, int i, int j, int k, float* g) {
+    g[0] = mesh_gradient_axis(at, i, j, k, 1, 0, 0, i, nx);
+    g[1] = mesh_gradient_axis(at, i, j, k, 0, 1, 0, j, ny);
+    g[2] = mesh_gradient_axis(at, i, j, k, 0, 0, 1, k, nz);
+}
+
+// the normal of the vertex at t on the edge along ax: g0, g1 the gradients at the edge's lower and upper end, inside0 = the lower
+// end is inside
+DANBO_HD void mesh_normal(const float* g0, const float* g1, float t, int ax, bool inside0, float* n) {
+    float g[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) g[c] = fmaf(t, sub_rn(g1[c], g0[c]), g0[c]);
+    const float m = fmaxf(fmaxf(fabsf(g[0]), fabsf(g[1])), fabsf(g[2]));
+    const bool finite = g[0] - g[0] == 0.f && g[1] - g[1] == 0.f && g[2] - g[2] == 0.f;       // (fmaxf drops a NaN)
+    if (!finite || !(m > 0.f)) {
+        const float e = inside0 ? 1.f : -1.f;
+        n[0] = ax == 0 ? e : 0.f; n[1] = ax == 1 ? e : 0.f; n[2] = ax == 2 ? e : 0.f;
+        return;
+    }
+    const float hx = div_rn(g[0], m), hy = div_rn(g[1], m), hz = div_rn(g[2], m);
+    const float len = sqrtf(add_rn(add_rn(mul_rn(hx, hx), mul_rn(hy, hy)), mul_rn(hz, hz)));
+    n[0] = div_rn(-hx, len); n[1] = div_rn(-hy, len); n[2] = div_rn(-hz, len);
+}
+
+// the normal of the vertex owned by the grid point (i, j, k) and the axis ax; g0 = mesh_gradient there (shared by the point's edges)
+DANBO_HD void mesh_vertex_normal(const MeshReader& at, int nx, int ny, int nz, int i, int j, int k, int ax, float iso, const float* g0,
+                                 float* n) {
+    const int i1 = i + (ax == 0), j1 = j + (ax == 1), k1 = k + (ax == 2);
+    const float s0 = at(i, j, k);
+    float g1[3];
+    mesh_gradient(at, nx, ny, nz, i1, j1, k1, g1);
+    mesh_normal(g0, g1, mesh_edge_t(s0, at(i1, j1, k1), iso), ax, mesh_inside(s0, iso), n);
 }
 
 // ---- the 256-case table (tools/gen_mc_table.py -> mc_table.inc) ----
@@ -151,6 +218,30 @@ inline int mesh_extract_host(const float* sigma, int nx, int ny, int nz, long st
                     if (t < cap_t) tris[3 * t + c % 3] = (int)(workspace[q] + mesh_popc3(g.emask(i + di, j + dj, k + dk) & ((1 << ax) - 1)));
                 }
                 T += mc_ntri(entry);
+            }
+    return 0;
+}
+
+// the normals of the vertices mesh_extract_host writes, float[V][3] in vertex order (the same grid and workspace)
+inline int mesh_normals_host(const float* sigma, int nx, int ny, int nz, long stride_x, long stride_y, float floor, float iso,
+                             const int32_t* workspace, float* normals, int cap_v) {
+    if (!sigma || !workspace || !normals || !mesh_dims_ok(nx, ny, nz, stride_x, stride_y, floor, iso) || cap_v < 0) return -22;
+    const MeshGrid g{sigma, nx, ny, nz, stride_x, stride_y, floor, iso};
+    const MeshReader at{sigma, stride_x, stride_y, floor};
+    long n = 0;
+    for (int i = 0; i < nx; ++i)
+        for (int j = 0; j < ny; ++j)
+            for (int k = 0; k < nz; ++k, ++n) {
+                const int em = g.emask(i, j, k);
+                if (!em) continue;
+                float g0[3];
+                mesh_gradient(at, nx, ny, nz, i, j, k, g0);
+                long v = workspace[n];
+                for (int ax = 0; ax < 3; ++ax) {
+                    if (!((em >> ax) & 1)) continue;
+                    if (v < cap_v) mesh_vertex_normal(at, nx, ny, nz, i, j, k, ax, iso, g0, normals + 3 * v);
+                    ++v;
+                }
             }
     return 0;
 }

@@ -42,6 +42,8 @@ def config_parser():
     p.add_argument('--mesh_res', type=int, default=255)
     p.add_argument('--mesh_radius', type=float, default=1.8)
     p.add_argument('--mesh_threshold', type=float, default=10.0, help='density of the extracted isosurface')
+    p.add_argument('--mesh_normals', action='store_true', help='with --render_mesh: per-vertex normals in the .ply')
+    p.add_argument('--mesh_colors', action='store_true', help='with --render_mesh: per-vertex colours (seen head-on) in the .ply')
     p.add_argument('--render_confd', action='store_true')
     p.add_argument('--render_entropy', action='store_true')
     p.add_argument('--selected_idxs', nargs='+', type=int, default=None)
@@ -255,19 +257,23 @@ def evaluate_metric(rgbs, accs, bboxes, gt_dict, basedir):
 
 
 @torch.no_grad()
-def render_mesh(basedir, render_kwargs, tensor_data, chunk=4096, radius=1.80, res=255, threshold=10.):
+def render_mesh(basedir, render_kwargs, tensor_data, chunk=4096, radius=1.80, res=255, threshold=10., normals=False, colors=False):
     """Density on a (res+1)^3 grid around every pose and its isosurface at `threshold` (reference :1266-1281: PyMCubes and trimesh
     there, the library's own extraction kernels and core/utils/mesh_io.py here): `meshes/NNN.ply`, vertices in [-0.5, 0.5]^3, and
-    the clamped grid as `meshes/NNN_sigma.npy`."""
+    the clamped grid as `meshes/NNN_sigma.npy`.  normals / colors (--mesh_normals / --mesh_colors) add per-vertex unit normals --
+    the gradient of the grid, where the reference's separate render_mesh.py sums face normals (compute_normal) -- and per-vertex
+    colours of the network seen along -normal (with the frame's frame code, where the network has them) to the vertex records."""
     caster = render_kwargs['ray_caster']
     os.makedirs(os.path.join(basedir, 'meshes'), exist_ok=True)
-    kps, skts, bones = tensor_data['kp'], tensor_data['skts'], tensor_data['bones']
+    kps, skts, bones, cams = tensor_data['kp'], tensor_data['skts'], tensor_data['bones'], tensor_data.get('cams')
     for i in range(len(kps)):
-        verts, faces, raw = caster(kps=kps[i:i + 1], skts=skts[i:i + 1], bones=bones[i:i + 1], radius=radius,
-                                   render_kwargs=render_kwargs['preproc_kwargs'], res=res, netchunk=chunk, threshold=threshold,
-                                   return_density=True, fwd_type='mesh_surface')
+        cam = None if cams is None else cams[i % cams.shape[0]:i % cams.shape[0] + 1]
+        verts, faces, *attrs, raw = caster(kps=kps[i:i + 1], skts=skts[i:i + 1], bones=bones[i:i + 1], radius=radius,
+                                           render_kwargs=render_kwargs['preproc_kwargs'], res=res, netchunk=chunk, threshold=threshold,
+                                           return_density=True, normals=normals, colors=colors, cams=cam, fwd_type='mesh_surface')
         np.save(os.path.join(basedir, 'meshes', f'{i:03d}_sigma.npy'), np.maximum(raw.cpu().numpy(), 0))
-        write_ply(os.path.join(basedir, 'meshes', f'{i:03d}.ply'), verts, faces)
+        write_ply(os.path.join(basedir, 'meshes', f'{i:03d}.ply'), verts, faces, normals=attrs[0] if normals else None,
+                  colors=attrs[-1] if colors else None)
 
 
 def run_render(argv=None):
@@ -283,7 +289,8 @@ def run_render(argv=None):
     basedir = os.path.join(args.outputdir, args.runname)
     os.makedirs(basedir, exist_ok=True)
     if args.render_mesh:
-        render_mesh(basedir, render_kwargs, tensor_data, res=args.mesh_res, radius=args.mesh_radius, threshold=args.mesh_threshold)
+        render_mesh(basedir, render_kwargs, tensor_data, res=args.mesh_res, radius=args.mesh_radius, threshold=args.mesh_threshold,
+                    normals=args.mesh_normals, colors=args.mesh_colors)
         return None
     render_kwargs = dict(render_kwargs, render_confd=args.render_confd, render_entropy=args.render_entropy)
     rgbs, _, accs, _, bboxes = render_path(render_kwargs=render_kwargs, chunk=nerf_args.chunk, ext_scale=nerf_args.ext_scale,

@@ -51,7 +51,8 @@ extern "C" {
  * danbo_composite_importance_pdf_fwd (the pdf of the two-network mode, single_net = False); danbo_composite_rays_fwd_act,
  * danbo_composite_importance_pdf_fwd_act, danbo_composite_merged_fwd_act, danbo_composite_bwd_lazy_act, danbo_render_frame_act
  * (the density activation: relu or softplus(x - shift), density_type = softplus); danbo_mesh_workspace_bytes, danbo_mesh_count,
- * danbo_mesh_extract (isosurface extraction on the density grid: --render_mesh ends in a mesh). */
+ * danbo_mesh_extract (isosurface extraction on the density grid: --render_mesh ends in a mesh); danbo_mesh_normals (vertex normals
+ * of the extracted mesh). */
 int danbo_abi_version(void);
 int danbo_device_info(int* cu_count, int* lds_bytes, char* arch, int arch_len);
 
@@ -964,6 +965,21 @@ int danbo_mesh_count(const float* sigma, int nx, int ny, int nz, long stride_x, 
 int danbo_mesh_extract(const float* sigma, int nx, int ny, int nz, long stride_x, long stride_y, float floor, float iso,
                        const void* workspace, float scale, float off_x, float off_y, float off_z,
                        float* verts /*[cap_v,3]*/, int cap_v, int* tris /*[cap_t,3]*/, int cap_t, void* stream);
+
+/* Vertex normals of the mesh danbo_mesh_extract writes (additive in ABI 9).  Replaces the first step of the reference's separate
+ * render_mesh.py, compute_normal -- face normals summed per vertex through `norm[faces[:, 0]] += n`, which with repeated indices
+ * keeps the last write only -- by the gradient of the implicit surface itself:
+ *   v(q) = the floored value at the grid point q (as above); d(a, b) = v(b) - v(a) in fp32, 0 where it is not finite;
+ *   gradient at a grid point q per axis a: 0.5 d(q - e_a, q + e_a) inside, d(q, q + e_a) on the low face, d(q - e_a, q) on the high;
+ *   at the vertex (lower end p, axis ax, t as above), per component: g = fma(t, g(p + e_ax) - g(p), g(p));
+ *   m = max |g_a|; where m is 0 or a component is not finite the normal is the unit vector along ax from the inside end to the
+ *   outside end (+e_ax if s0 >= iso, else -e_ax); else h = g / m, n = -h / sqrt(h . h): unit length, from high density to low, as
+ *   the triangles' orientation.  (csrc/mesh_math.hpp states the roundings; the kernel equals its serial restatement bit for bit.)
+ * Takes the same grid and the workspace danbo_mesh_count filled; writes normals [V,3] in vertex order and nothing at or beyond
+ * cap_v rows (cap_v = 0: nothing is launched).  Index-space normals: a uniform scale of the vertices leaves them as they are.
+ * DANBO_EINVAL before any launch: what danbo_mesh_extract rejects of the grid, a null or misaligned `normals`, a negative cap_v. */
+int danbo_mesh_normals(const float* sigma, int nx, int ny, int nz, long stride_x, long stride_y, float floor, float iso,
+                       const void* workspace, float* normals /*[cap_v,3]*/, int cap_v, void* stream);
 
 #ifdef __cplusplus
 }

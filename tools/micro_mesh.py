@@ -7,6 +7,11 @@ sphere.  Device events, warm-up, five blocks of at least 0.1 s each, the median 
   * the host path it replaces: device -> host copy of the grid + the serial extractor of csrc/mesh_math.hpp.
 
     python tools/micro_mesh.py [--res 255] > profiles/mesh_extract_measured.txt
+
+--normals: instead, on the same two grids, danbo_mesh_normals (k_mesh_normals) beside k_mesh_vertices alone (danbo_mesh_extract with
+a triangle capacity of 0) from the same run, and the normals against the serial restatement of csrc/mesh_math.hpp.
+
+    python tools/micro_mesh.py --normals > profiles/mesh_attrs_measured.txt
 """
 import argparse
 import ctypes
@@ -91,10 +96,45 @@ def measure(name, sigma, iso, floor, read_tbs):
     return ms_c + ms_e
 
 
+def measure_normals(name, sigma, iso, floor):
+    from core import _hip
+    import mesh_attr_ref
+    lib = _hip.lib()
+    nx, ny, nz = sigma.shape
+    P = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    ws = torch.empty(lib.danbo_mesh_workspace_bytes(nx, ny, nz), dtype=torch.uint8, device=DEV)
+    counts = torch.zeros(2, dtype=torch.int32, device=DEV)
+    grid = (P(sigma), nx, ny, nz, sigma.stride(0), sigma.stride(1), floor, iso)
+    assert lib.danbo_mesh_count(*grid, P(ws), P(counts), st) == 0
+    V, T = counts.tolist()
+    verts = torch.empty(max(V, 1), 3, dtype=torch.float32, device=DEV)
+    normals = torch.empty(max(V, 1), 3, dtype=torch.float32, device=DEV)
+
+    def vertices():
+        assert lib.danbo_mesh_extract(*grid, P(ws), 1.0, 0., 0., 0., P(verts), V, None, 0, st) == 0
+
+    def nrm():
+        assert lib.danbo_mesh_normals(*grid, P(ws), P(normals), V, st) == 0
+    ms_v, reps_v = timed_ms(vertices)
+    ms_n, reps_n = timed_ms(nrm)
+    print(f"{name}: grid {nx} x {ny} x {nz} (strides {tuple(sigma.stride())}), iso {iso:.6g}, floor {floor}, V {V}, T {T}")
+    print(f"{name}: k_mesh_vertices {ms_v:.4f} ms ({reps_v} launches per block); k_mesh_normals (danbo_mesh_normals) {ms_n:.4f} ms "
+          f"({reps_n} launches per block) = {ms_n / ms_v:.2f} x")
+    t0 = time.perf_counter()
+    want = mesh_attr_ref.host_normals(sigma.contiguous().cpu().numpy(), iso, floor)
+    t1 = time.perf_counter()
+    same = want.tobytes() == normals[:V].cpu().numpy().tobytes()
+    print(f"{name}: serial restatement {1e3 * (t1 - t0):.1f} ms (same bits as the kernel: {same})")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--res", type=int, default=255)
+    ap.add_argument("--normals", action="store_true", help="time danbo_mesh_normals beside k_mesh_vertices instead")
     args = ap.parse_args()
+    if args.normals:
+        return main_normals(args)
     probe = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "probe", "hbm_rate.py")], capture_output=True, text=True,
                            timeout=300, check=True).stdout
     print(probe.strip())
@@ -117,6 +157,21 @@ def main():
     n = args.res + 1
     sphere = torch.tensor(mesh_ref.sphere_grid((n, n, n), R=0.39 * n, centre=(0.497 * n, 0.502 * n, 0.493 * n)), device=DEV)
     measure("sphere", sphere, 0.0, float("-inf"), read_tbs)
+
+
+def main_normals(args):
+    from helpers import golden
+    from test_gpu_modules import build, T
+    import mesh_ref
+    g = golden("danbo_mesh")
+    caster, _ = build("h36m_zju/danbo_base.txt", g)
+    with torch.no_grad():
+        dens = caster(T(g["kps"][:1]), T(g["skts"][:1]), T(g["bones"][:1]), fwd_type="mesh", radius=float(g["radius"]), res=args.res)
+    pos = dens[dens > 0]
+    measure_normals("golden pose", dens, float(pos.median()) if pos.numel() else 0.0, 0.0)
+    n = args.res + 1
+    sphere = torch.tensor(mesh_ref.sphere_grid((n, n, n), R=0.39 * n, centre=(0.497 * n, 0.502 * n, 0.493 * n)), device=DEV)
+    measure_normals("sphere", sphere, 0.0, float("-inf"))
 
 
 if __name__ == "__main__":
