@@ -1,12 +1,26 @@
-"""ctypes binding of libdanbo_hip.so (C ABI declared in include/danbo_hip.h).
+"""ctypes binding of libdanbo_hip.so, derived from include/danbo_hip.h when this module is imported.
 
-The library is the only compute backend of this package: there is NO PyTorch/CPU fallback.
-`lib()` raises if the shared object is missing, and every wrapper in hip_ops raises if a
-tensor is not a CUDA(HIP) tensor.
+The header is the only statement of the C ABI.  `parse_header` reads the subset of C it is written in (stated at the top of the
+header) and this module builds from it, with nothing typed a second time:
+  SIGNATURES / RESTYPES   name -> argtypes / restype of every entry point, set on the library by `lib()`
+  the struct classes      one `ctypes.Structure` per `typedef struct`, under the header's name (DanboModel, DanboDwLayer, ...)
+  C                       every numeric `#define` and enumerator under the header's name (C.DANBO_J, C.DANBO_T_COUNT, ...)
+Every pointer, whatever it points to, is a `c_void_p` (`char*`: `c_char_p`): a parameter takes None, an address, `ptr(tensor)`,
+`ctypes.byref(x)` or a ctypes array.  A construct the parser does not know raises HeaderError at import and quotes the text; nothing
+is skipped.  A new entry point needs its declaration in the header and its implementation, and is then callable as
+`call("danbo_x", ...)`; a wrapper in hip_ops is optional.
+
+The header is $DANBO_HIP_HEADER, else danbo_hip.h beside the library, else include/danbo_hip.h of the source tree.  `lib()` refuses
+a library whose danbo_abi_version() is not the header's DANBO_ABI_VERSION (a stale build).
+
+The library is the only compute backend of this package: there is NO PyTorch/CPU fallback.  `lib()` raises if the shared object is
+missing, and every wrapper in hip_ops raises if a tensor is not a CUDA(HIP) tensor.
 """
 import ctypes
 import os
-from ctypes import c_long, c_char_p, c_float, c_int, c_size_t, c_void_p, POINTER
+import re
+from ctypes import c_char_p, c_float, c_int, c_void_p
+from types import SimpleNamespace
 
 import torch  # (before the library is opened: torch's bundled libamdhip64 is loaded first, so both share one HIP runtime)
 
@@ -17,151 +31,185 @@ P = c_void_p  # device pointer
 I = c_int
 F = c_float
 
-# name -> argtypes, exactly as declared in include/danbo_hip.h
-SIGNATURES = {
-    "danbo_abi_version": [],
-    "danbo_device_info": [POINTER(c_int), POINTER(c_int), c_char_p, I],
-    "danbo_pose_volumes_fwd": [P, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P],
-    "danbo_near_far_cylinder": [P, P, P, I, I, F, F, P, P, I, P, P, P, P],
-    "danbo_near_far_boxes": [P, P, P, P, P, I, I, P, P, P],
-    "danbo_coarse_samples": [P, P, I, I, P, P, P],
-    "danbo_bone_cull": [P, P, P, P, I, I, I, P, P, P, P, P, P, P, P, P, P, P],
-    "danbo_ray_bone_mask": [P, P, P, P, I, I, P, P, P, P, P, P],
-    "danbo_bone_gather_fwd": [P, P, P, P, I, I, I, P, P, P, P, P, P, I, P, P],
-    "danbo_assign_blend_fwd": [P, P, P, P, I, P, P, P, P, P, P, P, P, P, P],
-    "danbo_gather_assign_blend_fwd": [P, P, P, P, I, I, I, P, P, P, P, P, P, P, I, P, P, P, P, P, P, P, P, P, P],
-    "danbo_assign16_pack": [P, P, P, P, P],
-    "danbo_gather_assign_blend16_fwd": [P, P, P, P, I, I, I, P, P, P, P, P, P, P, I, P, P, P, P, P, P, P, P, P],
-    "danbo_mlp_pack": [POINTER(c_void_p), P, P, I, P, P, P],
-    "danbo_view_consts": [P, P, I, I, I, I, I, P, I, I, P, P, P, P, P, P, P, I, P, P, P, P, P, P],
-    "danbo_view_code_table": [P, P, I, I, I, P, P, P, P],
-    "danbo_mlp16_pack": [POINTER(c_void_p), P, P, P, P, I, P, P, P],
-    "danbo_pe_mlp16_fwd": [P, P, P, I, I, P, POINTER(c_void_p), P, P, P, P, P, P, P, P],
-    "danbo_transform_batch_pts": [P, P, c_long, I, I, I, I, P, P],
-    "danbo_optcodes_fwd": [P, I, I, P, I, c_long, I, P, P],
-    "danbo_mlp32_pack": [POINTER(c_void_p), P, P, P, P, I, P, P, P],
-    "danbo_pe_mlp32_fwd": [P, P, P, I, I, P, POINTER(c_void_p), P, P, P, P, P, P, P, P],
-    "danbo_pe_mlp_fwd": [P, P, P, I, I, P, POINTER(c_void_p), P, P, P, P, P, P, P, P, P],
-    "danbo_fill_raw": [P, I, I, P, P],
-    "danbo_composite_rays_fwd": [P, P, P, P, P, I, I, F, P, P, P, P, P, P, P, P, P],
-    "danbo_composite_rays_fwd_act": [P, P, P, P, P, I, I, F, P, P, P, P, P, P, P, P, I, F, P],
-    "danbo_importance_samples_rays": [P, P, I, I, I, P, P, P, P, P, P, P],
-    "danbo_composite_fwd": [P, P, P, I, I, F, P, P, P, P, P, P, P],
-    "danbo_composite_bwd": [P, P, P, I, I, F, P, P, P, P, P],
-    "danbo_bone_gather_bwd": [P, P, P, P, I, I, I, P, P, P, P, P, I, P, P, P, P],
-    "danbo_importance_samples": [P, P, I, I, I, P, P, P, P, P],
-    "danbo_importance_samples_pdf": [P, P, I, I, I, P, I, P, P, P, P, P, P],
-    "danbo_merge_samples": [P, P, P, I, I, I, I, P, P],
-    "danbo_composite_importance_fwd": [P, P, P, P, P, I, I, I, F, P, P, P, P, P, P, P, P, P, P, P, P, P],
-    "danbo_composite_importance_pdf_fwd": [P, P, P, P, P, I, I, I, F, P, P, I, P, P, P, P, P, P, P, P, P, P, P],
-    "danbo_composite_importance_pdf_fwd_act": [P, P, P, P, P, I, I, I, F, P, P, I, P, P, P, P, P, P, P, P, P, P, I, F, P],
-    "danbo_composite_merged_fwd": [P, P, P, P, P, P, P, P, I, I, I, F, P, P, P, P, P, P, P, P, P, P],
-    "danbo_composite_merged_fwd_act": [P, P, P, P, P, P, P, P, I, I, I, F, P, P, P, P, P, P, P, P, P, I, F, P],
-    "danbo_flat_rays": [P, P, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, P],
-    "danbo_anerf_encode_fwd": [P, P, P, P, I, I, I, P, P, P, F, I, c_long, I, P, P, P],
-    "danbo_anerf_encode_compact": [P, P, P, P, I, I, I, P, P, P, F, c_long, I, P, P, P],
-    "danbo_anerf_view_pe_fwd": [P, P, I, I, I, P, P],
-    "danbo_anerf_color_fwd": [P, I, P, P, P, P, I, I, I, I, I, I, P, P, P, I, P, P],
-    "danbo_linear16_set_trace": [P],
-    "danbo_linear16_packed_bytes": [I, I, I],
-    "danbo_linear16_pack": [P, c_long, c_long, I, I, I, P, P],
-    "danbo_linear16_fwd": [P, I, I, P, I, I, P, P, I, I, P, I, I, P, P],
-    "danbo_linear16_pack_frag": [P, c_long, c_long, I, I, I, I, P, P],
-    "danbo_linear16_fwd_frag": [P, I, I, P, I, I, P, P, I, I, P, I, I, P, I, P],
-    "danbo_linear16_pack_enc": [P, c_long, c_long, I, I, I, I, P, P],
-    "danbo_linear16_fwd_enc": [P, I, P, I, P, P, I, I, P, I, P, P],
-    "danbo_linear16_fwd_color": [P, I, P, P, I, I, P, P, P, P, I, I, I, I, P, P, P, P],
-    "danbo_render_frame_workspace": [I, I, I, I, I, I],
-    "danbo_render_frame": [P, P, I, I, P, P, c_size_t, P],
-    "danbo_render_frame_act": [P, P, I, I, P, P, c_size_t, I, F, P],
-    # ---- training step
-    "danbo_composite_bwd_lazy": [P, P, P, P, P, I, I, F, P, P, P, P, P],
-    "danbo_composite_bwd_lazy_act": [P, P, P, P, P, I, I, F, P, P, P, P, I, F, P],
-    "danbo_dw16_scratch_floats": [P, I, I],
-    "danbo_dw16": [P, I, I, P, I, P, P],
-    "danbo_gather_assign_blend16_train": [P, P, P, I, I, I, P, P, P, P, P, P, P, P, I, P, P, P, P, P, P, P, P],
-    "danbo_train_view_inputs": [P, P, I, I, I, I, I, P, I, I, P, P, I, P],
-    "danbo_train_loss_grad": [P, P, P, P, P, P, I, I, I, F, F, P, P, P, P, P, P],
-    "danbo_train_draw_unmerge": [P, P, P, P, P, P, P, I, I, I, P, P, P, P, P, P, P],
-    "danbo_train_mid": [P, P, P, P, P, P, I, I, I, I, I, F, F, F] + [P] * 25,
-    "danbo_train_bone_lists": [P, P, P, P, I, I, P, P, P],
-    "danbo_assign_blend_bwd": [P, P],
-    "danbo_pose_volumes_bwd": [P, I, I, I] + [P] * 24,
-    "danbo_adam_step": [P, P, P, P, c_long, F, F, F, F, F, F, F, P],
-    "danbo_random_draws": [P, c_long, P, c_long, F, P, P],
-    "danbo_gather_rows": [P, I, P, P],
-    "danbo_trunk_pack": [P, P],
-    "danbo_trunk_fwd": [P, P, I, P],
-    "danbo_trunk_bwd": [P, P, P],
-    "danbo_trunk_pe_column": [I],
-    "danbo_train_cview": [P, I, I, P, P, I, P, P],
-    "danbo_train_view_grads": [P, P, P, I, I, P, I, I, P, I, P, P, P, P, P],
-    "danbo_train_head_chain": [P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, P, P],
-    "danbo_train_workspace": [P, I, I, I, I, I],
-    "danbo_train_step": [P, P, P, P, c_size_t, P],
-    "danbo_train_step_phase": [P, P, P, P, c_size_t, I, P],
-    "danbo_train_workspace_view": [P, I, I, I, I, I, P, P],
-    "danbo_group_rows": [P, P, P, I, P],
-    # ---- A-NeRF on own kernels end to end (ABI 8)
-    "danbo_small_matmul": [P, c_long, c_long, P, c_long, c_long, P, I, I, I, P, c_long, P],
-    "danbo_anerf_view_wj_pack": [P, I, I, I, I, P, P],
-    "danbo_anerf_view_consts_fwd": [P, P, I, I, I, P, I, P, P],
-    "danbo_anerf_view_consts_bwd_scratch_floats": [I, I, I],
-    "danbo_anerf_view_consts_bwd": [P, P, I, I, I, P, I, P, I, I, P, P],
-    "danbo_anerf_color_train_fwd": [P, I, P, P, P, I, I, I, I, P, P, P, I, P, P, P],
-    "danbo_anerf_color_bwd_part_floats": [I, I],
-    "danbo_anerf_color_bwd": [P, P, P, I, I, I, I, P, P, P, P, P, I, P, P, I, P, P],
-    "danbo_anerf_rgb_reduce": [P, c_long, I, P, P, P],
-    "danbo_anerf_ray_table": [P, I, I, I, P, P, I, P, I, I, P, P],
-    "danbo_anerf_code_grads": [P, P, I, I, I, P, I, P, I, I, P, P, P, P, P],
-    "danbo_anerf_relu_mask": [P, P, c_long, P, P, P, P, P, P],
-    "danbo_anerf_unmerge": [P, P, P, I, I, I, P, P, P],
-    "danbo_anerf_encode_fwd_dtau": [P, P, P, P, I, I, I, P, P, P, P, I, c_long, I, P, P, P],
-    "danbo_anerf_train_workspace": [P, I, I, I, I, I],
-    "danbo_anerf_train_step": [P, P, P, P, c_size_t, P],
-    "danbo_anerf_train_workspace_view": [P, I, I, I, I, I, P, P],
-    "danbo_assign16_set_trace": [P],
-    # ---- isosurface extraction on the density grid
-    "danbo_mesh_workspace_bytes": [I, I, I],
-    "danbo_mesh_count": [P, I, I, I, c_long, c_long, F, F, P, P, P],
-    "danbo_mesh_extract": [P, I, I, I, c_long, c_long, F, F, P, F, F, F, F, P, I, P, I, P],
-    "danbo_mesh_normals": [P, I, I, I, c_long, c_long, F, F, P, P, I, P],
-}
-# everything else returns int (0 = ok)
-RESTYPES = {"danbo_mesh_workspace_bytes": c_size_t, "danbo_render_frame_workspace": c_size_t, "danbo_train_workspace": c_size_t,
-            "danbo_dw16_scratch_floats": c_long, "danbo_anerf_train_workspace": c_size_t,
-            "danbo_anerf_view_consts_bwd_scratch_floats": c_long, "danbo_anerf_color_bwd_part_floats": c_long}
+
+class HeaderError(ValueError):
+    """include/danbo_hip.h left the subset of C that parse_header reads"""
 
 
-class DanboModel(ctypes.Structure):
-    """mirror of `struct DanboModel` in include/danbo_hip.h"""
-    _fields_ = ([(n, P) for n in ("g_w0", "g_adjw0", "g_b0", "g_w1", "g_adjw1", "g_b1", "g_w2", "g_b2", "g_w3", "g_b3")]
-                + [("L_graph", I), ("graph_width", I), ("align", P), ("axis_scale", P), ("assign16", P)]
-                + [(n, P) for n in ("a_b0", "a_b1", "a_w2", "a_b2")] + [("mlp16", P), ("pts_b", P * 8)]
-                + [(n, P) for n in ("alpha_w", "alpha_b", "rgb_w", "rgb_b", "views_w_ray_t", "views_b_eff", "framecodes",
-                                    "mean_code", "code_table", "empty_consts")]
-                + [(n, I) for n in ("n_codes", "code_size", "L_view", "ray_mode", "normalise")]
-                + [("density_scale", F), ("use_volume_near_far", I), ("flat_rays_ok", I)])
+_SCALARS = {"int": c_int, "long": ctypes.c_long, "long long": ctypes.c_longlong, "size_t": ctypes.c_size_t, "float": c_float,
+            **{f"{u}int{n}_t": getattr(ctypes, f"c_{u}int{n}") for u in ("", "u") for n in (8, 16, 32, 64)}}
+_TAIL = r"((?:\*\s*(?:const\b\s*)?)*)(\w+)\s*(?:\[\s*(\w*)\s*\])?$"          # `* const* name[N]` -> stars, name, array length
+_DECL = re.compile(r"(?:const\s+)?(long\s+long|\w+)\b\s*" + _TAIL)        # `const T* const* name[N]` -> T, stars, name, array length
+_MORE = re.compile(_TAIL)                                                 # the further declarators of `T *a, *b`
+_PROTO = re.compile(r"(int|long|size_t)\s+(\w+)\s*\((.*)\)$", re.S)
+_STRUCT = re.compile(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*(\w+)$", re.S)
+_ENUM = re.compile(r"enum\s+\w+\s*\{([^{}]*)\}$", re.S)
+_TOKEN = re.compile(r"\s*(?:(0[xX][0-9a-fA-F]+|\d+)[uUlL]*(?![\w.])|((?:\d+\.\d*|\.\d+|\d+)(?:[eE][-+]?\d+)?)([fF]?)(?![\w.])"
+                    r"|([A-Za-z_]\w*)|(<<|>>|[-+*()|&~]))")
 
 
-MAX_ROW_SPANS = 12
+def _expr(expr, sources):
+    """a constant expression of C as Python source: integer / float literals, + - * << >> | & ~, parentheses, and the names in
+    `sources` replaced by their text as the preprocessor replaces a macro"""
+    out, pos = [], 0
+    while pos < len(expr.rstrip()):
+        m = _TOKEN.match(expr, pos)
+        if not m:
+            raise HeaderError(f"constant expression not understood: {expr.strip()!r}")
+        integer, real, f32, name, op = m.groups()
+        if name is not None and name not in sources:
+            raise HeaderError(f"{name!r} in {expr.strip()!r} is not a constant defined above it")
+        out.append(repr(int(integer, 0)) if integer else repr(c_float(float(real)).value if f32 else float(real)) if real
+                   else sources[name] if name else op)
+        pos = m.end()
+    return " ".join(out)
 
 
-class DanboRowSpan(ctypes.Structure):
-    _fields_ = [("src", P), ("dst_word", c_long), ("src_row_stride_words", c_long), ("rows", I), ("row_words", I)]
+def _value(source, text):
+    try:
+        return eval(source, {"__builtins__": {}})     # literals and operators only: _expr matched every token
+    except Exception:
+        raise HeaderError(f"constant expression not understood: {text.strip()!r}") from None
 
 
-class DanboRays(ctypes.Structure):
-    _fields_ = ([(n, P) for n in ("rays_o", "rays_d", "skts", "bones", "cyls", "cam_idx", "near_in", "far_in")]
-                + [("R", I), ("G", I), ("chunk", I)])
+def _ctype(base, stars, structs, text):
+    base = " ".join(base.split())
+    if stars:
+        if base not in _SCALARS and base not in structs and base not in ("void", "char"):
+            raise HeaderError(f"unknown type {base!r} in {text!r}")
+        return c_char_p if base == "char" and stars.count("*") == 1 else c_void_p
+    if base not in _SCALARS:
+        raise HeaderError(f"unknown scalar type {base!r} in {text!r}")
+    return _SCALARS[base]
 
 
-class DanboFrameOut(ctypes.Structure):
-    _fields_ = [(n, P) for n in ("rgb_map", "disp_map", "acc_map", "alpha", "weights", "rgb0", "disp0", "acc0", "alpha0")]
+def _fields(body, constants, structs):
+    """`const float *a, *b; int n; T* p[8];` -> [(name, ctype)]"""
+    fields = []
+    for stmt in filter(None, (s.strip() for s in body.split(";"))):
+        first, *more = (d.strip() for d in stmt.split(","))
+        matches = [_DECL.match(first)] + [_MORE.match(d) for d in more]
+        if None in matches:
+            raise HeaderError(f"struct field not understood: {stmt!r}")
+        for m in matches:
+            stars, name, n = m.groups()[-3:]
+            t = _ctype(matches[0].group(1), stars, structs, stmt)
+            if n is not None:
+                if n not in constants and not n.isdigit():
+                    raise HeaderError(f"array length {n!r} in {stmt!r} is not a constant defined above it")
+                t = t * int(constants.get(n, n))
+            fields.append((name, t))
+    return fields
 
 
+def _params(text, structs):
+    types = []
+    for p in (p.strip() for p in text.split(",") if text.strip() not in ("", "void")):
+        m = _DECL.match(p)
+        if not m:
+            raise HeaderError(f"parameter not understood: {p!r}")
+        base, stars, _, n = m.groups()
+        t = _ctype(base, stars, structs, p)
+        types.append(t if n is None else c_void_p)       # `T x[N]`, `T x[]`: a pointer
+    return types
 
-# ---- training step (include/danbo_hip.h: enum DanboTrainTensor and the Danbo{LinearEx,PackDesc,DwLayer,AssignBwd,Train*} structs)
+
+def parse_header(text):
+    """-> (functions {name: (restype, [argtypes])}, structs {name: [(field, ctype)]}, constants {name: int | float}) of a header
+    written in the subset of C that include/danbo_hip.h states at its top; raises HeaderError on anything else."""
+    functions, structs, constants, sources = {}, {}, {}, {}
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    if "/*" in text or "*/" in text or "\\\n" in text:
+        raise HeaderError("unterminated comment or continued line")
+    code, guard, open_ifs = [], None, []
+    for line in text.split("\n"):
+        s = line.strip()
+        if not s.startswith("#"):
+            if "__cplusplus" not in open_ifs:
+                code.append(line)
+            elif s not in ("", 'extern "C" {', "}"):
+                raise HeaderError(f"only the extern \"C\" guard may stand under #ifdef __cplusplus: {s!r}")
+            continue
+        word, rest = re.match(r"#\s*(\w*)\s*(.*)$", s).groups()
+        if word == "include" and re.match(r"<\w+\.h>$", rest):
+            pass
+        elif word == "ifndef" and guard is None and re.match(r"\w+$", rest):        # the include guard, once
+            guard = rest
+            open_ifs.append(rest)
+        elif word == "ifdef" and rest == "__cplusplus":
+            open_ifs.append(rest)
+        elif word == "endif" and not rest and open_ifs:
+            open_ifs.pop()
+        elif word == "define" and rest == guard:
+            pass
+        elif word == "define" and re.match(r"\w+\s+\S", rest):
+            name, expr = rest.split(None, 1)
+            if name in constants:
+                raise HeaderError(f"{name} is defined twice")
+            sources[name] = _expr(expr, sources)
+            constants[name] = _value(sources[name], s)
+        else:
+            raise HeaderError(f"preprocessor line not understood: {s!r}")
+    if open_ifs:
+        raise HeaderError(f"the #if of {open_ifs[-1]} is never closed")
+
+    decl, depth = [], 0
+    for piece in re.split(r"([;{}])", "\n".join(code)):
+        depth += (piece == "{") - (piece == "}")
+        if piece != ";" or depth:
+            decl.append(piece)
+            continue
+        d = "".join(decl).strip()
+        decl = []
+        if m := _PROTO.match(d):
+            restype, name, params = m.groups()
+            if name in functions:
+                raise HeaderError(f"{name} is declared twice")
+            functions[name] = (_SCALARS[restype], _params(params, structs))
+        elif m := _STRUCT.match(d):
+            if m.group(1) != m.group(3) or m.group(1) in structs:
+                raise HeaderError(f"struct tag and typedef name differ, or the struct is declared twice: {m.group(1)!r} / {m.group(3)!r}")
+            structs[m.group(1)] = _fields(m.group(2), constants, structs)
+        elif m := _ENUM.match(d):
+            nxt = 0
+            for item in filter(None, (e.strip() for e in m.group(1).split(","))):
+                name, _, expr = (x.strip() for x in item.partition("="))
+                if not re.match(r"[A-Za-z_]\w*$", name) or name in constants:
+                    raise HeaderError(f"enumerator not understood, or defined twice: {item!r}")
+                constants[name] = nxt = _value(_expr(expr, sources), item) if expr else nxt
+                sources[name] = repr(nxt)
+                nxt += 1
+        else:
+            raise HeaderError(f"declaration not understood: {d!r}")
+    if "".join(decl).strip():
+        raise HeaderError(f"text left over after the last declaration: {''.join(decl).strip()!r}")
+    return functions, structs, constants
+
+
+def _header_path():
+    env = os.environ.get("DANBO_HIP_HEADER")
+    tried = [env] if env else [os.path.join(os.path.dirname(LIB_PATH), "danbo_hip.h"),
+                               os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "danbo_hip.h")]
+    for p in tried:
+        if os.path.exists(p):
+            return p
+    raise RuntimeError("danbo_hip.h not found (the ctypes binding is derived from it): tried " + ", ".join(tried)
+                       + "; set DANBO_HIP_HEADER or put the header beside the library")
+
+
+HEADER_PATH = _header_path()
+with open(HEADER_PATH) as _f:
+    _functions, _structs, _constants = parse_header(_f.read())
+SIGNATURES = {name: argtypes for name, (_, argtypes) in _functions.items()}
+RESTYPES = {name: restype for name, (restype, _) in _functions.items()}
+STRUCTS = {name: type(name, (ctypes.Structure,), {"_fields_": fields, "__doc__": f"struct {name} of include/danbo_hip.h"})
+           for name, fields in _structs.items()}
+globals().update(STRUCTS)              # _hip.DanboModel, _hip.DanboDwLayer, ...
+C = SimpleNamespace(**_constants)
+MAX_ROW_SPANS = C.DANBO_MAX_ROW_SPANS
+ANERF_MAX_D = C.DANBO_ANERF_MAX_D
+
+# ---- training step: the state_dict key of every slot of DanboTrainModel.p / .g (enum DanboTrainTensor; the names are Python's)
 TRAIN_TENSORS = (
     ["graph_net.layers.0.lin.weight", "graph_net.layers.0.adj_w", "graph_net.layers.0.bias", "graph_net.layers.1.lin.weight",
      "graph_net.layers.1.adj_w", "graph_net.layers.1.bias", "graph_net.layers.2.weight", "graph_net.layers.2.bias",
@@ -171,75 +219,12 @@ TRAIN_TENSORS = (
     + [f"pts_linears.{i}.weight" for i in range(8)] + [f"pts_linears.{i}.bias" for i in range(8)]
     + ["alpha_linear.weight", "alpha_linear.bias", "feature_linear.weight", "feature_linear.bias", "views_linears.0.weight",
        "views_linears.0.bias", "rgb_linear.weight", "rgb_linear.bias", "framecodes.codes.weight"])
-N_TRAIN_TENSORS = len(TRAIN_TENSORS)   # DANBO_T_COUNT
-
-
-class DanboDwLayer(ctypes.Structure):
-    _fields_ = ([(n, P) for n in ("dy", "x1", "x2", "dy_maxabs", "gw", "gw2", "gb", "gb2")]
-                + [(n, I) for n in ("ldy", "ld1", "ld2", "N", "K1", "K2", "split_n", "frag", "gw_ld", "gw_col0", "x1_pe")])
-
-
-class DanboAssignBwd(ctypes.Structure):
-    _fields_ = ([(n, P) for n in ("rays_o", "rays_d", "z_c", "z_f", "skts", "align", "axis_scale", "volumes")]
-                + [(n, I) for n in ("R", "S", "Sf", "G", "rows_cap")]
-                + [(n, P) for n in ("row_sample", "row_ray", "cnt", "lists", "cntb", "h_rows", "d_h", "label_c", "label_f", "bits_c",
-                                    "bits_f", "w0", "adj_w", "adj", "b0", "w1", "b1", "w2", "b2", "g_w0", "g_adj_w", "g_b0", "g_w1",
-                                    "g_b1", "g_w2", "g_b2", "g_vol", "g_scale")]
-                + [("c_ss", F), ("loss", P), ("d_p", P)])
-
-
-class DanboTrunkWeights(ctypes.Structure):
-    _fields_ = ([("pts_w", P * 8), ("pts_b", P * 8)]
-                + [(n, P) for n in ("alpha_w", "alpha_b", "feature_w", "feature_b", "views_w", "views_b", "rgb_w", "rgb_b")]
-                + [("view_ch", I)] + [(n, P) for n in ("packed", "wfv", "b_eff", "wmax", "winv")])
-
-
-class DanboTrunkRows(ctypes.Structure):
-    _fields_ = ([(n, P) for n in ("cnt", "row_sample", "h_rows", "cview")] + [(n, I) for n in ("R", "S", "Sf", "rows_cap")]
-                + [("rows_pad", c_long)]
-                + [(n, P) for n in ("y", "pe", "relu", "hv", "hv_bits", "raw_rows", "raw_c", "raw_f", "raw_empty", "row_ray",
-                                    "d_raw_c", "d_raw_f", "d_raw_rows", "dz", "dpre_v", "d_alpha4", "d_h", "maxabs")])
-
-
-class DanboTrainModel(ctypes.Structure):
-    _fields_ = ([("p", P * N_TRAIN_TENSORS), ("g", P * N_TRAIN_TENSORS), ("g_flat", P), ("n_flat", c_long)]
-                + [(n, P) for n in ("g_adj0", "g_adj1", "a_adj", "align", "init_scale")]
-                + [(n, I) for n in ("L_graph", "graph_width", "L_view", "L_voxel", "ray_mode", "normalise", "n_codes", "code_size",
-                                    "view_ch", "use_volume_near_far", "loss_mse", "use_background")]
-                + [(n, F) for n in ("density_scale", "rgb_loss_coef", "coarse_weight", "soft_softmax_coef", "vol_scale_penalty")])
-
-
-class DanboTrainBatch(ctypes.Structure):
-    _fields_ = ([(n, P) for n in ("rays_o", "rays_d", "skts", "bones", "cyls", "near_in", "far_in", "cam_idx", "target", "bgs",
-                                  "t_rand", "u_rand", "noise_c", "noise_f")]
-                + [(n, I) for n in ("R", "G", "S", "Sf", "chunk")]
-                + [(n, P) for n in ("rng_state", "rng_uniform", "rng_normal")]
-                + [("n_uniform", ctypes.c_longlong), ("n_normal", ctypes.c_longlong), ("normal_std", F)])
-
-
-class DanboTrainOut(ctypes.Structure):
-    _fields_ = [(n, P) for n in ("rgb_map", "disp_map", "acc_map", "alpha", "weights", "rgb0", "disp0", "acc0", "alpha0", "loss",
-                                 "counts")]
-
-
-ANERF_MAX_D = 8
-
-
-class DanboAnerfTrainModel(ctypes.Structure):
-    """mirror of `struct DanboAnerfTrainModel` in include/danbo_hip.h"""
-    _fields_ = ([(n, I) for n in ("D", "W", "VW", "skip", "L", "L_view", "n_codes", "code_size")]
-                + [("pts_w", P * ANERF_MAX_D), ("pts_b", P * ANERF_MAX_D)]
-                + [(n, P) for n in ("alpha_w", "alpha_b", "feature_w", "feature_b", "views_w", "views_b", "rgb_w", "rgb_b", "codes")]
-                + [("g_pts_w", P * ANERF_MAX_D), ("g_pts_b", P * ANERF_MAX_D)]
-                + [(n, P) for n in ("g_alpha_w", "g_alpha_b", "g_feature_w", "g_feature_b", "g_views_w", "g_views_b", "g_rgb_w", "g_rgb_b",
-                                    "g_codes", "g_flat")]
-                + [("n_flat", c_long)] + [(n, P) for n in ("align", "cutoff", "tau")]
-                + [("loss_mse", I), ("use_background", I)] + [(n, F) for n in ("density_scale", "rgb_loss_coef", "coarse_weight")])
-
-
-class DanboTrainView(ctypes.Structure):
-    _fields_ = [(n, P) for n in ("z_coarse", "z_fine", "z_sorted", "order", "bits_coarse", "bits_fine")]
-
+N_TRAIN_TENSORS = C.DANBO_T_COUNT
+_anchors = {"graph_net.axis_scale": C.DANBO_T_AXIS_SCALE, "prob_linears.layers.0.lin.weight": C.DANBO_T_A_W0,
+            "pts_linears.0.weight": C.DANBO_T_PTS_W0, "pts_linears.0.bias": C.DANBO_T_PTS_B0, "alpha_linear.weight": C.DANBO_T_ALPHA_W,
+            "framecodes.codes.weight": C.DANBO_T_CODES}
+if len(TRAIN_TENSORS) != N_TRAIN_TENSORS or any(TRAIN_TENSORS.index(k) != i for k, i in _anchors.items()):
+    raise HeaderError(f"TRAIN_TENSORS does not line up with enum DanboTrainTensor of {HEADER_PATH}")
 
 _lib = None
 
@@ -255,7 +240,10 @@ def lib():
         for name, argtypes in SIGNATURES.items():
             fn = getattr(l, name)
             fn.argtypes = argtypes
-            fn.restype = RESTYPES.get(name, c_int)
+            fn.restype = RESTYPES[name]
+        if l.danbo_abi_version() != C.DANBO_ABI_VERSION:
+            raise RuntimeError(f"{LIB_PATH} has ABI version {l.danbo_abi_version()}, {HEADER_PATH} declares {C.DANBO_ABI_VERSION}: "
+                               "the library is stale, rebuild it with `make -C danbo-pytorch_amd/csrc`")
         _lib = l
     return _lib
 
@@ -276,4 +264,9 @@ class HipError(RuntimeError):
 
 def check(code, name):
     if code != 0:
-        raise HipError(f"{name} failed with code {code}" + (" (invalid argument)" if code == -22 else ""))
+        raise HipError(f"{name} failed with code {code}" + (" (invalid argument)" if code == C.DANBO_EINVAL else ""))
+
+
+def call(name, *args):
+    """one entry point that returns a status: raises HipError unless it is 0"""
+    check(getattr(lib(), name)(*args), name)

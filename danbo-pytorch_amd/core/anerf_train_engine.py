@@ -114,8 +114,7 @@ class AnerfTrainEngine(DanboTrainEngine):
         return _hip.lib().danbo_anerf_train_workspace(ctypes.byref(m), R, G, S, Sf, chunk)
 
     def _c_step(self, m, bt, o, phase, stream):
-        _hip.check(_hip.lib().danbo_anerf_train_step(ctypes.byref(m), ctypes.byref(bt), ctypes.byref(o), ptr(self._ws), self._ws.numel(), stream),
-                   "danbo_anerf_train_step")
+        _hip.call("danbo_anerf_train_step", ctypes.byref(m), ctypes.byref(bt), ctypes.byref(o), ptr(self._ws), self._ws.numel(), stream)
 
     def forward_backward(self, *a, **k):
         tau, tau_v = float(self.net.pe_fn.tau), float(self.net.dirs_pe_fn.tau)
@@ -136,6 +135,5 @@ class AnerfTrainEngine(DanboTrainEngine):
     def workspace_view(self, R, G, S, Sf):
         """device views of the last step's sampling decisions (z_coarse [R,S], z_fine [R,Sf], z_sorted, order [R,S+Sf])"""
         v = _hip.DanboTrainView()
-        _hip.check(_hip.lib().danbo_anerf_train_workspace_view(ctypes.byref(self._model()), R, G, S, Sf, R, ptr(self._ws), ctypes.byref(v)),
-                   "danbo_anerf_train_workspace_view")
+        _hip.call("danbo_anerf_train_workspace_view", ctypes.byref(self._model()), R, G, S, Sf, R, ptr(self._ws), ctypes.byref(v))
         return v

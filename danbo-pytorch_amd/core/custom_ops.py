@@ -114,9 +114,8 @@ def bone_gather_bwd(volumes: torch.Tensor, axis_scale: torch.Tensor, pts: torch.
     d_vol = torch.zeros(volumes.shape, dtype=torch.float32, device=volumes.device)
     d_sc = torch.zeros(axis_scale.shape, dtype=torch.float32, device=volumes.device)
     if n > 0:
-        _hip.check(_hip.lib().danbo_bone_gather_bwd(None, None, None, _p(pts), R, S, G, _p(skts), _p(align), _p(axis_scale), _p(volumes),
-                                                    _p(rows), n, _p(g.contiguous().float()), _p(d_vol), _p(d_sc), ops._stream()),
-                   "danbo_bone_gather_bwd")
+        _hip.call("danbo_bone_gather_bwd", None, None, None, _p(pts), R, S, G, _p(skts), _p(align), _p(axis_scale), _p(volumes), _p(rows),
+                  n, _p(g.contiguous().float()), _p(d_vol), _p(d_sc), ops._stream())
     return d_vol, d_sc
 
 
@@ -172,9 +171,8 @@ def pose_volumes(bones: torch.Tensor, L_graph: int, params: List[torch.Tensor]) 
     vol = torch.empty(G, ops.J, ops.VOL, device=bones.device, dtype=torch.float32)
     # (named: a temporary handed to _p() is freed -- and its block re-used by the next temporary -- before the launch)
     adjw0, adjw1 = (a["aw0"] * a["a0"]).contiguous(), (a["aw1"] * a["a1"]).contiguous()
-    _hip.check(_hip.lib().danbo_pose_volumes_fwd(_p(bones), G, int(L_graph), W, _p(a["w0"]), _p(adjw0), _p(a["b0"]), _p(a["w1"]), _p(adjw1),
-                                                 _p(a["b1"]), _p(a["w2"]), _p(a["b2"]), _p(a["w3"]), _p(a["b3"]), _p(scratch), _p(vol),
-                                                 ops._stream()), "danbo_pose_volumes_fwd")
+    _hip.call("danbo_pose_volumes_fwd", _p(bones), G, int(L_graph), W, _p(a["w0"]), _p(adjw0), _p(a["b0"]), _p(a["w1"]), _p(adjw1),
+              _p(a["b1"]), _p(a["w2"]), _p(a["b2"]), _p(a["w3"]), _p(a["b3"]), _p(scratch), _p(vol), ops._stream())
     return vol, scratch
 
 
@@ -194,11 +192,10 @@ def pose_volumes_bwd(bones: torch.Tensor, L_graph: int, params: List[torch.Tenso
     names = ("w0", "aw0", "b0", "w1", "aw1", "b1", "w2", "b2", "w3", "b3")
     g = {k: torch.zeros(a[k].shape, device=dev, dtype=torch.float32) for k in names}     # (adj_w / b0 / b1 are accumulated into)
     bwd_scratch = torch.empty(2 * G * ops.J * W, device=dev, dtype=torch.float32)
-    _hip.check(_hip.lib().danbo_pose_volumes_bwd(
-        _p(bones), G, int(L_graph), W, _p(a["w0"]), _p(a["aw0"]), _p(a["a0"]), _p(a["b0"]), _p(a["w1"]), _p(a["aw1"]), _p(a["a1"]), _p(a["b1"]),
-        _p(a["w2"]), _p(a["w3"]), _p(ops._f32(scratch, "scratch")), _p(ops._f32(g_vol, "g_vol")), _p(g["w0"]), _p(g["aw0"]), _p(g["b0"]),
-        _p(g["w1"]), _p(g["aw1"]), _p(g["b1"]), _p(g["w2"]), _p(g["b2"]), _p(g["w3"]), _p(g["b3"]), _p(bwd_scratch), ops._stream()),
-        "danbo_pose_volumes_bwd")
+    _hip.call("danbo_pose_volumes_bwd", _p(bones), G, int(L_graph), W, _p(a["w0"]), _p(a["aw0"]), _p(a["a0"]), _p(a["b0"]), _p(a["w1"]),
+              _p(a["aw1"]), _p(a["a1"]), _p(a["b1"]), _p(a["w2"]), _p(a["w3"]), _p(ops._f32(scratch, "scratch")),
+              _p(ops._f32(g_vol, "g_vol")), _p(g["w0"]), _p(g["aw0"]), _p(g["b0"]), _p(g["w1"]), _p(g["aw1"]), _p(g["b1"]), _p(g["w2"]),
+              _p(g["b2"]), _p(g["w3"]), _p(g["b3"]), _p(bwd_scratch), ops._stream())
     w0, aw0, a0, b0, w1, aw1, a1, b1, w2, b2, w3, b3 = params
     return [g[k].reshape(t.shape) for k, t in zip(names, (w0, aw0, b0, w1, aw1, b1, w2, b2, w3, b3))]
 
@@ -304,8 +301,7 @@ def assign_blend_bwd(volumes: torch.Tensor, axis_scale: torch.Tensor, pts: torch
         bits32 = bits.reshape(-1).contiguous()
         lists = torch.empty(ops.J, n, device=dev, dtype=torch.int32)
         cntb = torch.zeros(ops.J, device=dev, dtype=torch.int32)
-        _hip.check(_hip.lib().danbo_train_bone_lists(_p(bits32), _p(bits32), _p(rows32), _p(cnt), 0, n, _p(lists), _p(cntb), ops._stream()),
-                   "danbo_train_bone_lists")
+        _hip.call("danbo_train_bone_lists", _p(bits32), _p(bits32), _p(rows32), _p(cnt), 0, n, _p(lists), _p(cntb), ops._stream())
         zeros_m = z32(M)
         ab = _hip.DanboAssignBwd()
         keep = dict(o=ops._f32(pts, "pts").reshape(M, 3), d=z32(M, 3), z=zeros_m, lab=torch.zeros(M, device=dev, dtype=torch.uint8),
@@ -319,7 +315,7 @@ def assign_blend_bwd(volumes: torch.Tensor, axis_scale: torch.Tensor, pts: torch
                          g_vol=g["vol"], g_scale=g["scale"], loss=keep["loss"], d_p=keep["dp"]).items():
             setattr(ab, k, v.data_ptr())
         ab.R, ab.S, ab.Sf, ab.G, ab.rows_cap, ab.c_ss = M, 1, 1, G, n, 0.0
-        _hip.check(_hip.lib().danbo_assign_blend_bwd(ctypes.byref(ab), ops._stream()), "danbo_assign_blend_bwd")
+        _hip.call("danbo_assign_blend_bwd", ctypes.byref(ab), ops._stream())
     w0, adj_w, adj, b0, w1, b1, w2, b2 = params
     return [g["vol"].reshape(volumes.shape), g["scale"].reshape(axis_scale.shape), g["w0"].reshape(w0.shape), g["adj_w"].reshape(adj_w.shape),
             g["b0"].reshape(b0.shape), g["w1"].reshape(w1.shape), g["b1"].reshape(b1.shape), g["w2"].reshape(w2.shape),
@@ -367,9 +363,9 @@ def _trunk_structs(h, row_ray, vin, params, need_bwd):
     n, R = h.shape[0], vin.shape[0]
     pad = (n + 127) // 128 * 128 + 128
     f32 = lambda *s: torch.empty(s, device=dev, dtype=torch.float32)  # noqa: E731
-    buf = dict(packed=torch.empty(_hip_trunk_bytes(), device=dev, dtype=torch.uint8), wfv=f32(128 * 256), b_eff=f32(128),
+    buf = dict(packed=torch.empty(ops.TRUNK_PACKED_BYTES, device=dev, dtype=torch.uint8), wfv=f32(128 * 256), b_eff=f32(128),
                wmax=torch.zeros(16, device=dev), winv=f32(16), cnt=torch.zeros(8, device=dev, dtype=torch.int32),
-               h16=torch.zeros(n, 16, device=dev), cview=f32(R, 128), y=f32(8, pad * 256), pe=f32(pad * 224),
+               h16=torch.zeros(n, 16, device=dev), cview=f32(R, 128), y=f32(8, pad * 256), pe=f32(pad * ops.TRUNK_PE_WIDTH),
                relu=torch.empty(8, pad * 4, device=dev, dtype=torch.int64), hv=f32(pad * 128),
                hv_bits=torch.empty(pad * 4, device=dev, dtype=torch.int32), raw_rows=f32(n, 4), raw_dense=f32(max(R, 1), 4),
                row_ray_out=torch.empty(n, device=dev, dtype=torch.int32))
@@ -398,10 +394,6 @@ def _trunk_structs(h, row_ray, vin, params, need_bwd):
     return buf, w, r
 
 
-def _hip_trunk_bytes():
-    return (74 + 76) * 32768       # DANBO_TRUNK_PACKED_BYTES
-
-
 def _vin_padded(vin):
     """[R, view_ch] -> row stride a multiple of 4 floats with 8 floats of slack (the view-gradient kernel reads 8 columns at a time)"""
     R, C = vin.shape
@@ -418,12 +410,11 @@ def pe_mlp(h: torch.Tensor, row_ray: torch.Tensor, vin: torch.Tensor, params: Li
     params = [p.detach().float().contiguous() for p in params]
     h, vin = h.detach().float().contiguous(), vin.detach().float().contiguous()
     buf, w, r = _trunk_structs(h, row_ray, vin, params, need_bwd=False)
-    lib, st = _hip.lib(), ops._stream()
-    _hip.check(lib.danbo_trunk_pack(ctypes.byref(w), st), "danbo_trunk_pack")
+    st = ops._stream()
+    _hip.call("danbo_trunk_pack", ctypes.byref(w), st)
     vp, ld = _vin_padded(vin)
-    _hip.check(lib.danbo_train_cview(_p(vp), ld, vin.shape[1], _p(params[20]), _p(buf["b_eff"]), vin.shape[0], _p(buf["cview"]), st),
-               "danbo_train_cview")
-    _hip.check(lib.danbo_trunk_fwd(ctypes.byref(w), ctypes.byref(r), 0, st), "danbo_trunk_fwd")
+    _hip.call("danbo_train_cview", _p(vp), ld, vin.shape[1], _p(params[20]), _p(buf["b_eff"]), vin.shape[0], _p(buf["cview"]), st)
+    _hip.call("danbo_trunk_fwd", ctypes.byref(w), ctypes.byref(r), 0, st)
     return buf["raw_rows"]
 
 
@@ -442,18 +433,18 @@ def pe_mlp_bwd(h: torch.Tensor, row_ray: torch.Tensor, vin: torch.Tensor, params
     n, R, C = h.shape[0], vin.shape[0], vin.shape[1]
     dev = h.device
     buf, w, r = _trunk_structs(h, row_ray, vin, params, need_bwd=True)
-    lib, st = _hip.lib(), ops._stream()
-    _hip.check(lib.danbo_trunk_pack(ctypes.byref(w), st), "danbo_trunk_pack")
+    st = ops._stream()
+    _hip.call("danbo_trunk_pack", ctypes.byref(w), st)
     vp, ld = _vin_padded(vin)
-    _hip.check(lib.danbo_train_cview(_p(vp), ld, C, _p(params[20]), _p(buf["b_eff"]), R, _p(buf["cview"]), st), "danbo_train_cview")
-    _hip.check(lib.danbo_trunk_fwd(ctypes.byref(w), ctypes.byref(r), 0, st), "danbo_trunk_fwd")
+    _hip.call("danbo_train_cview", _p(vp), ld, C, _p(params[20]), _p(buf["b_eff"]), R, _p(buf["cview"]), st)
+    _hip.call("danbo_trunk_fwd", ctypes.byref(w), ctypes.byref(r), 0, st)
     buf["cnt"][4] = n                                  # total rows (the step's second pass would have set it)
     # ---- input-gradient chain on d raw per row
     d_raw_rows = torch.zeros(n, 4, device=dev)
     d_raw_rows.copy_(g_raw.float())
     r.d_raw_rows = d_raw_rows.data_ptr()
     r.d_raw_c = r.d_raw_f = None
-    _hip.check(lib.danbo_trunk_bwd(ctypes.byref(w), ctypes.byref(r), st), "danbo_trunk_bwd")
+    _hip.call("danbo_trunk_bwd", ctypes.byref(w), ctypes.byref(r), st)
     # ---- weight gradients (k_dw16): the layer list of the training step (csrc/k_train.hip describe_dw)
     g = [torch.zeros_like(p) for p in params]
     g_wfv, g_beff = torch.zeros(128, 256, device=dev), torch.zeros(128, device=dev)
@@ -466,8 +457,8 @@ def pe_mlp_bwd(h: torch.Tensor, row_ray: torch.Tensor, vin: torch.Tensor, params
     for l in range(8):
         common = dict(dy=dz_of(l), ldy=256, N=256, dy_maxabs=mx[l:].data_ptr(), gw=g[l].data_ptr(), frag=3)
         if l in (0, 5):
-            layers.append(D(x1=buf["pe"].data_ptr(), ld1=224, K1=224, x1_pe=1, gw_ld=195 if l == 0 else 451, gw_col0=0, gb=g[8 + l].data_ptr(),
-                            **common))
+            layers.append(D(x1=buf["pe"].data_ptr(), ld1=ops.TRUNK_PE_WIDTH, K1=ops.TRUNK_PE_WIDTH, x1_pe=1, gw_ld=195 if l == 0 else 451,
+                            gw_col0=0, gb=g[8 + l].data_ptr(), **common))
             if l == 5:
                 layers.append(D(x1=y_of(4), ld1=256, K1=256, gw_ld=451, gw_col0=195, gb=None, **common))
         else:
@@ -481,14 +472,14 @@ def pe_mlp_bwd(h: torch.Tensor, row_ray: torch.Tensor, vin: torch.Tensor, params
                     gw=g[22].data_ptr(), gb=g[23].data_ptr()))
     L = (D * len(layers))(*layers)
     slices = 8
-    scratch = torch.empty(lib.danbo_dw16_scratch_floats(L, len(layers), slices), device=dev)
-    _hip.check(lib.danbo_dw16(L, len(layers), n, _p(buf["cnt"][4:]), slices, _p(scratch), st), "danbo_dw16")
+    scratch = torch.empty(_hip.lib().danbo_dw16_scratch_floats(L, len(layers), slices), device=dev)
+    _hip.call("danbo_dw16", L, len(layers), n, _p(buf["cnt"][4:]), slices, _p(scratch), st)
     # ---- per-ray view gradients, then the chain rule of the merged feature / view layer
     d_cview = torch.zeros(R, 128, device=dev)
-    _hip.check(lib.danbo_train_view_grads(_p(buf["dpre_v"]), _p(buf["row_ray_out"]), _p(buf["cnt"]), n, R, _p(vp), ld, C, None, 0, _p(d_cview),
-                                          None, _p(g[20]), None, st), "danbo_train_view_grads")
-    _hip.check(lib.danbo_train_head_chain(_p(g_wfv), _p(g_beff), None, _p(params[18]), _p(params[19]), _p(params[20]), C, 0, 0, 0,
-                                          _p(g[18]), _p(g[19]), _p(g[20]), _p(g[21]), None, None, st), "danbo_train_head_chain")
+    _hip.call("danbo_train_view_grads", _p(buf["dpre_v"]), _p(buf["row_ray_out"]), _p(buf["cnt"]), n, R, _p(vp), ld, C, None, 0,
+              _p(d_cview), None, _p(g[20]), None, st)
+    _hip.call("danbo_train_head_chain", _p(g_wfv), _p(g_beff), None, _p(params[18]), _p(params[19]), _p(params[20]), C, 0, 0, 0, _p(g[18]),
+              _p(g[19]), _p(g[20]), _p(g[21]), None, None, st)
     d_vin = ops.small_matmul(d_cview, params[20][:, 256:])     # [R,128] x [128, view_ch]: per RAY, tiny (danbo_small_matmul)
     return [buf["d_h"][:, :15].contiguous(), d_vin] + g
 

@@ -9,14 +9,21 @@ import ctypes
 import torch
 
 from . import _hip
-from ._hip import ptr as _p, stream as _stream  # noqa: F401  (the names the wrappers and the tests use)
+from ._hip import call as _call, ptr as _p, stream as _stream  # noqa: F401  (the names the wrappers and the tests use)
 
-J = 24
-VOL = 240
-FEAT = 15
-RAY_FLAT_VMAX = 1e4          # DANBO_RAY_FLAT_VMAX (include/danbo_hip.h)
-H_STRIDE = 16
-MLP_PACKED_FLOATS = 659456
+# constants of include/danbo_hip.h under the names the wrappers, the engines and the tests use
+J = _hip.C.DANBO_J
+VOL = _hip.C.DANBO_VOL
+FEAT = _hip.C.DANBO_FEAT
+RAY_FLAT_VMAX = _hip.C.DANBO_RAY_FLAT_VMAX
+H_STRIDE = _hip.C.DANBO_H_STRIDE
+MLP_PACKED_FLOATS = _hip.C.DANBO_MLP_PACKED_FLOATS
+ASSIGN16_PACKED_BYTES = _hip.C.DANBO_ASSIGN16_PACKED_BYTES
+MLP16_PACKED_BYTES = _hip.C.DANBO_MLP16_PACKED_BYTES      # 74 chunks + trailer (winv, wmax, W_fv)
+ANERF_ENC_FLOATS = _hip.C.DANBO_ANERF_ENC_FLOATS          # the encoder's compact table: [24][4] + [24][2] floats per sample
+LINEAR16_ENC_K = _hip.C.DANBO_LINEAR16_ENC_K              # k-slots of the recomputed density inputs (14 k-steps)
+TRUNK_PACKED_BYTES = _hip.C.DANBO_TRUNK_PACKED_BYTES
+TRUNK_PE_WIDTH = _hip.C.DANBO_TRUNK_PE_WIDTH
 VIEW_W = 128
 
 
@@ -40,10 +47,6 @@ def _ptr_array(tensors):
     for i, t in enumerate(tensors):
         arr[i] = t.data_ptr()
     return arr
-
-
-def _call(name, *args):
-    _hip.check(getattr(_hip.lib(), name)(*args), name)
 
 
 # --------------------------------------------------------------------------------------
@@ -183,9 +186,6 @@ def gather_assign_blend(geo, volumes, bits, aw, lst=None, cnt=None, n=None, want
     return h, confd
 
 
-ASSIGN16_PACKED_BYTES = 262144
-
-
 _SMPL_PARENTS = [0, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16, 17, 18, 19, 20, 21]
 _ADJ_CHECKED = set()
 
@@ -239,7 +239,7 @@ def gather_assign_blend16(geo, volumes, bits, aw, packed16, lst=None, cnt=None, 
 
 
 def mlp_pack(pts_w, feature_w, views_w):
-    """pts_w: 8 tensors; views_w [128, 256+Cv] -> (packed [659456], views_w_ray_t [Cv,128])."""
+    """pts_w: 8 tensors; views_w [128, 256+Cv] -> (packed [MLP_PACKED_FLOATS], views_w_ray_t [Cv,128])."""
     dev = feature_w.device
     Cv = views_w.shape[1] - 256
     packed = torch.empty(MLP_PACKED_FLOATS, device=dev, dtype=torch.float32)
@@ -283,9 +283,6 @@ def pe_mlp(h, S, packed, pts_b, alpha_w, alpha_b, feature_b, cview, rgb_w, rgb_b
     return aux_out
 
 
-MLP16_PACKED_BYTES = 2424832 + 128 + 128 * 256 * 4      # 74 chunks + trailer (winv, wmax, W_fv): include/danbo_hip.h
-
-
 def mlp16_pack(pts_w, feature_w, feature_b, views_w, views_b, form=16):
     """fp16 hi/lo fragment packing for pe_mlp16 (form 16) / pe_mlp32 (form 32) -> (uint8 buffer [MLP16_PACKED_BYTES], views_b_eff [128])."""
     dev = feature_w.device
@@ -315,7 +312,7 @@ def fill_raw(raw_empty, S):
 
 
 RELU = ("relu", 0.0)
-_ACT_TYPES = {"relu": 0, "softplus": 1}      # DANBO_DENSITY_RELU / DANBO_DENSITY_SOFTPLUS (include/danbo_hip.h)
+_ACT_TYPES = {"relu": _hip.C.DANBO_DENSITY_RELU, "softplus": _hip.C.DANBO_DENSITY_SOFTPLUS}
 
 
 def density_act(fn):
@@ -536,10 +533,6 @@ def anerf_encode(rays_o, rays_d, skts, align, cutoff, tau, L, row0, nrows, z=Non
     _call("danbo_anerf_encode_fwd", *map(_p, geo), R, S, skts.shape[0], _p(skts), _p(_f32(align, "align")),
           _p(_f32(cutoff, "cutoff")), float(tau), int(L), int(row0), int(nrows), _p(x0), _p(w), _stream())
     return x0, w
-
-
-ANERF_ENC_FLOATS = 144     # the encoder's compact table: [24][4] + [24][2] floats per sample (csrc/k_anerf.hip)
-LINEAR16_ENC_K = 448       # k-slots of the recomputed density inputs (14 k-steps)
 
 
 def anerf_encode_compact(rays_o, rays_d, skts, align, cutoff, tau, row0, nrows, z=None, pts=None, out=None):

@@ -282,8 +282,8 @@ class DanboTrainEngine:
         return _hip.lib().danbo_train_workspace(ctypes.byref(m), R, G, S, Sf, chunk)
 
     def _c_step(self, m, bt, o, phase, stream):
-        _hip.check(_hip.lib().danbo_train_step_phase(ctypes.byref(m), ctypes.byref(bt), ctypes.byref(o), ptr(self._ws), self._ws.numel(),
-                                                     phase, stream), "danbo_train_step")
+        _hip.call("danbo_train_step_phase", ctypes.byref(m), ctypes.byref(bt), ctypes.byref(o), ptr(self._ws), self._ws.numel(), phase,
+                  stream)
 
     def _own_seed(self):
         """the seed of THIS rank's stream: torch's CUDA generator seed of the device, mixed with the RANK: ranks that were
@@ -466,9 +466,8 @@ class DanboTrainEngine:
         self.t += 1
         # the step's scalars are kernel ARGUMENTS (danbo_adam_step, ABI 2): the host may run any number of steps ahead of the GPU
         # (sync_stats=False) without a later step's bias corrections reaching an earlier step's launch
-        _hip.check(_hip.lib().danbo_adam_step(ptr(self.flat_p), ptr(self.flat_g), ptr(self.flat_m), ptr(self.flat_v), self.n_train,
-                                              float(lr), 1.0 - b1 ** self.t, math.sqrt(1.0 - b2 ** self.t), float(grad_scale),
-                                              float(b1), float(b2), float(grp['eps']), _hip.stream()), "danbo_adam_step")
+        _hip.call("danbo_adam_step", ptr(self.flat_p), ptr(self.flat_g), ptr(self.flat_m), ptr(self.flat_v), self.n_train, float(lr),
+                  1.0 - b1 ** self.t, math.sqrt(1.0 - b2 ** self.t), float(grad_scale), float(b1), float(b2), float(grp['eps']), _hip.stream())
         # torch.optim.Adam's per-parameter `step` entries (distinct CPU tensors, _adopt_optimizer_state): one fused in-place add
         torch._foreach_add_(self._step_tensors, 1.0)
         # the kernel wrote the parameters behind torch's back: bump their version counters, which the eval engine's packed weight

@@ -55,10 +55,8 @@ class GatherFn(torch.autograd.Function):
         d_sc = torch.zeros(axis_scale.shape, dtype=torch.float32, device=volumes.device)
         g = g.contiguous().float()
         if ctx.n > 0:
-            _hip.check(_hip.lib().danbo_bone_gather_bwd(
-                _p(geo.rays_o), _p(geo.rays_d), _p(geo.z), _p(geo.pts), geo.R, geo.S, geo.G, _p(geo.skts),
-                _p(geo.align), _p(axis_scale), _p(volumes.contiguous()), _p(rows), ctx.n, _p(g), _p(d_vol), _p(d_sc),
-                ops._stream()), "danbo_bone_gather_bwd")
+            _hip.call("danbo_bone_gather_bwd", _p(geo.rays_o), _p(geo.rays_d), _p(geo.z), _p(geo.pts), geo.R, geo.S, geo.G, _p(geo.skts),
+                      _p(geo.align), _p(axis_scale), _p(volumes.contiguous()), _p(rows), ctx.n, _p(g), _p(d_vol), _p(d_sc), ops._stream())
         return d_vol, d_sc, None, None
 
 
@@ -131,9 +129,8 @@ class Linear16Fn(torch.autograd.Function):
             layers.append(D(x1=x2.data_ptr(), ld1=K2, K1=K2, gw_col0=K1, gb=None, **common))
         L = (D * len(layers))(*layers)
         slices = 8
-        lib = _hip.lib()
-        scratch = torch.empty(lib.danbo_dw16_scratch_floats(L, len(layers), slices), device=dz.device)
-        _hip.check(lib.danbo_dw16(L, len(layers), M, None, slices, _p(scratch), ops._stream()), "danbo_dw16")
+        scratch = torch.empty(_hip.lib().danbo_dw16_scratch_floats(L, len(layers), slices), device=dz.device)
+        _hip.call("danbo_dw16", L, len(layers), M, None, slices, _p(scratch), ops._stream())
         return dx1, dx2, gw, (gb if ctx.has_bias else None), None, None
 
 
@@ -188,10 +185,9 @@ class AnerfColorFn(torch.autograd.Function):
         head[:, VW] = alpha.reshape(-1)
         hv = torch.empty(n, VW, device=featv.device, dtype=torch.float32)
         raw = torch.empty(R, S, 4, device=featv.device, dtype=torch.float32)
-        lib = _hip.lib()
-        _hip.check(lib.danbo_anerf_color_train_fwd(_p(head), VW + 4, _p(w), _p(C.contiguous()), _p(table_ray.contiguous()), R, R, S, VW,
-                                                   _p(rgb_w.detach().contiguous()), _p(rgb_b.detach().contiguous()), head[:, VW:].data_ptr(), VW + 4,
-                                                   _p(hv), _p(raw), ops._stream()), "danbo_anerf_color_train_fwd")
+        _hip.call("danbo_anerf_color_train_fwd", _p(head), VW + 4, _p(w), _p(C.contiguous()), _p(table_ray.contiguous()), R, R, S, VW,
+                  _p(rgb_w.detach().contiguous()), _p(rgb_b.detach().contiguous()), head[:, VW:].data_ptr(), VW + 4, _p(hv), _p(raw),
+                  ops._stream())
         ctx.save_for_backward(hv, w, rgb_w.detach().contiguous())
         ctx.R, ctx.S, ctx.VW = R, S, VW
         return raw
@@ -209,13 +205,12 @@ class AnerfColorFn(torch.autograd.Function):
         d_alpha4 = torch.empty(n, 4, device=dev)
         dC = torch.empty(24, R, VW, device=dev)
         d_pre_ray = torch.empty(R, VW, device=dev)
-        lib = _hip.lib()
-        nf = lib.danbo_anerf_color_bwd_part_floats(R, VW)
+        nf = _hip.lib().danbo_anerf_color_bwd_part_floats(R, VW)
         part = torch.empty(nf, device=dev)
-        _hip.check(lib.danbo_anerf_color_bwd(_p(d_raw), _p(hv), _p(w), R, R, S, VW, _p(rgb_w), _p(mx), _p(sig), _p(d_featv), _p(d_alpha4), 4,
-                                             _p(dC), _p(d_pre_ray), 0, _p(part), ops._stream()), "danbo_anerf_color_bwd")
+        _hip.call("danbo_anerf_color_bwd", _p(d_raw), _p(hv), _p(w), R, R, S, VW, _p(rgb_w), _p(mx), _p(sig), _p(d_featv), _p(d_alpha4), 4,
+                  _p(dC), _p(d_pre_ray), 0, _p(part), ops._stream())
         g_rgb_w, g_rgb_b = torch.empty(3, VW, device=dev), torch.empty(3, device=dev)
-        _hip.check(lib.danbo_anerf_rgb_reduce(_p(part), nf, VW, _p(g_rgb_w), _p(g_rgb_b), ops._stream()), "danbo_anerf_rgb_reduce")
+        _hip.call("danbo_anerf_rgb_reduce", _p(part), nf, VW, _p(g_rgb_w), _p(g_rgb_b), ops._stream())
         return d_featv / sig, (d_alpha4[:, 0] / sig).reshape(n, 1), dC, d_pre_ray, g_rgb_w, g_rgb_b, None, None, None
 
 

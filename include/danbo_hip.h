@@ -11,6 +11,20 @@
  * Each entry cites the reference code (file:line under the reference tree) it replaces.
  * J = 24 bones everywhere.  "pose" g of ray r is r / (R / G) (equal contiguous groups,
  * core/encoders.py:465-468, core/networks/gnn_backbone.py:792-794).
+ *
+ * THIS FILE IS READ BY A PROGRAM.  danbo-pytorch_amd/core/_hip.py parses it when the package is imported and derives its whole
+ * ctypes binding from it -- argument and result types, struct layouts, constants -- so that nothing is typed twice.  The parser
+ * knows the subset of C used below and refuses to import on anything else, quoting the text.  Stay within:
+ *   - comments anywhere; #include <x.h>; the include guard; the extern "C" guard under #ifdef __cplusplus; no other conditional,
+ *     no function-like macro, no continued line
+ *   - #define NAME <expression> on one line, and one enum with items `NAME` / `NAME = <expression>`: integer and float literals
+ *     (1e4f), names defined above, + - * << >> | & ~ and parentheses
+ *   - typedef struct Name { ... } Name; with fields `[const] T name;`, pointers `T* p`, `T *a, *b`, `T* const* p`, arrays
+ *     `T* p[8]`, `T* p[NAME]`; no nested struct, union or bit-field
+ *   - prototypes `int | long | size_t name(parameters);` with parameters written like fields, or `(void)`; no function pointers
+ *   - T: int, long, long long, size_t, float, the <stdint.h> integers; behind a `*` also void, char and a struct declared above
+ * Python passes every pointer as a plain address.  After a change, tests/test_abi_binding.py checks what the parser derived against
+ * the host compiler's view of this file.  Any change of a declared signature or struct raises DANBO_ABI_VERSION.
  */
 #ifndef DANBO_HIP_H
 #define DANBO_HIP_H
@@ -53,6 +67,7 @@ extern "C" {
  * (the density activation: relu or softplus(x - shift), density_type = softplus); danbo_mesh_workspace_bytes, danbo_mesh_count,
  * danbo_mesh_extract (isosurface extraction on the density grid: --render_mesh ends in a mesh); danbo_mesh_normals (vertex normals
  * of the extracted mesh). */
+#define DANBO_ABI_VERSION 9   /* what danbo_abi_version() of a library built from this header returns; the binding refuses another */
 int danbo_abi_version(void);
 int danbo_device_info(int* cu_count, int* lds_bytes, char* arch, int arch_len);
 
