@@ -11,6 +11,8 @@
 // the density activation of an `_act` entry point (danbo_hip.h): a known type and a finite shift, before any launch
 #define DANBO_CHECK_DENSITY_ACT(act, shift) \
     DANBO_CHECK_ARG(((act) == DANBO_DENSITY_RELU || (act) == DANBO_DENSITY_SOFTPLUS) && (shift) - (shift) == 0.f)
+// a C call made of C calls: the first non-zero return code is the caller's
+#define DANBO_TRY(call) do { const int rc_ = (call); if (rc_ != 0) return rc_; } while (0)
 #define DANBO_LAUNCH_RET() do { hipError_t e_ = hipGetLastError(); return e_ == hipSuccess ? 0 : (int)e_; } while (0)
 
 // Opt a kernel into more than 64 KB of dynamic LDS.  The attribute is per DEVICE: the "done" mask is keyed by the calling
@@ -47,6 +49,11 @@
 namespace danbo {
 
 constexpr int WAVE = 64;
+// the register-tuple types of the MFMA operands and of the 16-byte loads / stores: one spelling each, for every translation unit
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 // Compute units of the calling thread's current device (hipDeviceAttributeMultiprocessorCount, cached per device): the
 // persistent kernels size their grids from it.  256 on a full MI355X; partitioned (CPX / DPX) or harvested parts report less.
 // Development switches (fault bisection, stream-order experiments, A/B of a packing) read the environment only in a
@@ -72,6 +79,23 @@ static inline int num_cu() {
     }
     return n;
 }
+
+// Carves the intermediates of one C call out of a caller-provided workspace, every one at a 256-byte boundary of it.  Without a
+// workspace it only counts: take() returns nullptr and `used` ends as the bytes a real one needs (+ 256 for its own alignment).
+struct Carver {
+    char* base = nullptr;
+    size_t used = 0;
+    Carver() {}
+    explicit Carver(void* workspace) : base(reinterpret_cast<char*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255)) {}
+    void align() { used = (used + 255) & ~(size_t)255; }
+    template <class T>
+    T* take(size_t n) {
+        align();
+        T* p = base ? reinterpret_cast<T*>(base + used) : nullptr;
+        used += n * sizeof(T);
+        return p;
+    }
+};
 
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 
@@ -217,7 +241,6 @@ __device__ __forceinline__ int resolve_count(const int32_t* count, int n_cap) {
 // the asm MFMA chunks of mlp16_core.hpp start with `s_nop 1` for the same reason).
 template <class H8>
 __device__ __forceinline__ void split8_mix(const float* v, H8& hi, H8& lo) {
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     u32x4 h, l;
 #pragma unroll
     for (int p = 0; p < 4; ++p) {

@@ -91,7 +91,7 @@ __device__ __forceinline__ void composite_fwd_sweep(const float4* __restrict__ r
             carry = mul_rn(carry, __shfl(p, 63, 64));
         }
         rr[c] = sigmoidf_(rw.x); rg[c] = sigmoidf_(rw.y); rb[c] = sigmoidf_(rw.z);
-        cr[c] = rr[c] * 1.002f - 0.001f; cg[c] = rg[c] * 1.002f - 0.001f; cb[c] = rb[c] * 1.002f - 0.001f;
+        cr[c] = rgb_affine(rr[c]); cg[c] = rgb_affine(rg[c]); cb[c] = rgb_affine(rb[c]);
         acc += wave_sum(act ? a * T[c] : 0.f);
     }
     st.acc = acc;

@@ -7,7 +7,7 @@
 // The view layer's 648 per-sample inputs are PE(dir)[ray, joint] * w[sample, joint]: the product with
 // views_linears.0 factorises into per-ray, per-joint vectors C[ray, j, :] (24 x 224 floats, made once
 // per ray) and a 24-term weighted sum per sample -- 5 376 MACs instead of 145 152 per sample.
-#include "common.hpp"
+#include "anerf_wave.hpp"
 
 namespace danbo {
 
@@ -106,42 +106,18 @@ __global__ __launch_bounds__(AN_BLOCK) void k_anerf_encode(const float* __restri
     }
 }
 
-// reference: transform_batch_rays (encoders.py:305-317) -> VecNormEncoder -> the frequency part of
-// CutoffEmbedder._embed with dist_inputs (cutoff_embedder.py:156-166); the cutoff weight is applied per
-// sample in k_anerf_color.  E[ray][b*72 + 3j + k], b = 0: d, 1+2l: sin(2^l d), 2+2l: cos(2^l d)
+// E[ray][b*72 + 3j + k], b = 0: d, 1+2l: sin(2^l d), 2+2l: cos(2^l d) (av_ray_pe, anerf_wave.hpp); the cutoff weight is
+// applied per sample in k_anerf_color
 __global__ __launch_bounds__(256) void k_anerf_view_pe(const float* __restrict__ rays_d, const float* __restrict__ skts,
                                                        int R, int G, int L, float* __restrict__ E) {
-    const int rays_per_pose = R / G;
     const int stride = (1 + 2 * L) * 3 * J;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < (long)R * J; i += (long)gridDim.x * blockDim.x) {
         const int r = (int)(i / J), j = (int)(i % J);
-        const float* M = skts + ((size_t)min(r / rays_per_pose, G - 1) * J + j) * 16;
-        const float d[3] = {rays_d[3 * r], rays_d[3 * r + 1], rays_d[3 * r + 2]};
-        float q[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-            q[a] = add_rn(add_rn(mul_rn(M[4 * a], d[0]), mul_rn(M[4 * a + 1], d[1])), mul_rn(M[4 * a + 2], d[2]));
-        const float nrm = norm3_torch(q[0], q[1], q[2]);
-        const float den = fmaxf(nrm, 1e-12f);
-        float* out = E + (size_t)r * stride + 3 * j;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float u = div_rn(q[k], den);
-            out[k] = u;
-            for (int l = 0; l < L; ++l) {
-                float sn, cs;
-                sincosf(mul_rn(u, (float)(1 << l)), &sn, &cs);
-                out[(1 + 2 * l) * 3 * J + k] = sn;
-                out[(2 + 2 * l) * 3 * J + k] = cs;
-            }
-        }
+        av_ray_pe(rays_d, skts, R, G, L, r, j, E + (size_t)r * stride + 3 * j, 3 * J);
     }
 }
 
-// reference: the view branch of NeRF.inference (nerf.py:196-209) on encode_views' output (nerf.py:252-279).
-// One wavefront per ray: the ray's 24 x VW joint vectors stay in registers while its S samples stream by.
-//   x[c]   = relu(featv[row][c] + table[cam][c] + sum_j w[row][j] * C[j][ray][c])
-//   raw    = (rgb_w x + rgb_b, alpha[row])
+// the colour head with the table row of the ray's camera (anerf_color_body, anerf_wave.hpp)
 constexpr int AN_VW_MAX = 256;  // 4 columns per lane
 __global__ __launch_bounds__(256) void k_anerf_color(const float* __restrict__ featv, int ldf, const float* __restrict__ w,
                                                      const float* __restrict__ C, const float* __restrict__ table,
@@ -149,77 +125,7 @@ __global__ __launch_bounds__(256) void k_anerf_color(const float* __restrict__ f
                                                      int ray0, int nrays, int S, int VW,
                                                      const float* __restrict__ rgb_w, const float* __restrict__ rgb_b,
                                                      const float* __restrict__ alpha, int lda, float* __restrict__ raw_out) {
-    const int lane = threadIdx.x & 63;
-    const int wave_global = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
-    const int nwaves = (gridDim.x * blockDim.x) >> 6;
-    float rw[3][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + 64 * i;
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) rw[ch][i] = c < VW ? rgb_w[ch * VW + c] : 0.f;
-    }
-    const float rb0 = rgb_b[0], rb1 = rgb_b[1], rb2 = rgb_b[2];
-    for (int rl = wave_global; rl < nrays; rl += nwaves) {
-        const int ray = ray0 + rl;
-        float cj[J][4];
-#pragma unroll
-        for (int j = 0; j < J; ++j)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int c = lane + 64 * i;
-                cj[j][i] = c < VW ? C[((size_t)j * R_total + ray) * VW + c] : 0.f;
-            }
-        long code = n_codes;  // the mean code (Optcodes eval with idx < 0)
-        if (cam_idx) {
-            const long idx = cam_idx[ray];
-            if (idx >= 0) code = idx < n_codes ? idx : n_codes - 1;
-        }
-        float tb[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int c = lane + 64 * i;
-            tb[i] = c < VW ? table[(size_t)code * VW + c] : 0.f;
-        }
-        // four samples per trip: all their loads (16 feature values and 4 x 24 cutoff weights) are issued before the first
-        // FMA, so one memory latency is paid per four samples instead of per sample (a wavefront walks its ray alone)
-        constexpr int U = 4;
-        for (int s0 = 0; s0 < S; s0 += U) {
-            float x[U][4], wj[U][J], al[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const size_t row = (size_t)rl * S + min(s0 + u, S - 1);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int c = lane + 64 * i;
-                    x[u][i] = c < VW ? featv[row * ldf + c] : 0.f;
-                }
-#pragma unroll
-                for (int j = 0; j < J; ++j) wj[u][j] = w[row * J + j];
-                al[u] = alpha[row * lda];
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) x[u][i] = (lane + 64 * i) < VW ? x[u][i] + tb[i] : 0.f;
-#pragma unroll
-                for (int j = 0; j < J; ++j)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) x[u][i] = fmaf(wj[u][j], cj[j][i], x[u][i]);
-                float pr = 0.f, pg = 0.f, pb = 0.f;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float xr = fmaxf(x[u][i], 0.f);
-                    pr = fmaf(xr, rw[0][i], pr);
-                    pg = fmaf(xr, rw[1][i], pg);
-                    pb = fmaf(xr, rw[2][i], pb);
-                }
-                pr = wave_total(pr); pg = wave_total(pg); pb = wave_total(pb);   // DPP scan: no LDS-crossbar shuffles
-                if (lane == 0 && s0 + u < S)
-                    reinterpret_cast<float4*>(raw_out)[(size_t)ray * S + s0 + u] = make_float4(pr + rb0, pg + rb1, pb + rb2, al[u]);
-            }
-        }
-    }
+    anerf_color_body<false>(featv, ldf, w, C, table, cam_idx, n_codes, R_total, ray0, nrays, S, VW, rgb_w, rgb_b, alpha, lda, nullptr, raw_out);
 }
 
 }  // namespace danbo

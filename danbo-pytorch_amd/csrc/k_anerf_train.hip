@@ -3,7 +3,7 @@
 //
 //   k_anerf_view_consts        C[j, ray, :] = views_linears.0[:, view columns of joint j] . PE(unit local ray direction)      (render + training)
 //   k_anerf_view_consts_bwd    d views_linears.0[:, view columns] = sum_rays PE(dir)^T dC                                       (slices + fixed-order sum)
-//   k_anerf_color<TRAIN>       k_anerf.hip's colour head with a per-RAY table row and hv = relu(pre_v) kept for the backward
+//   k_anerf_color_train        k_anerf.hip's colour head with a per-RAY table row and hv = relu(pre_v) kept for the backward
 //   k_anerf_color_bwd          d raw -> d featv, d alpha (scaled for the fp16-split GEMMs), dC, d pre_ray, partial d rgb_linear
 //   k_anerf_ray_table / k_anerf_code_grads / k_anerf_code_rows / k_anerf_code_scatter     the frame-code part of the view layer
 //   k_anerf_relu_mask          dz_l = dY_l . [y_l > 0], re-centred by a power of two, running max
@@ -14,37 +14,13 @@
 //
 // Every sum over rays / samples that ends in a parameter gradient is taken in a FIXED order (slices written to scratch and added
 // by one thread per entry, leaders instead of atomics for the frame codes): two runs of a step give the same bits.
-#include "common.hpp"
+#include "anerf_wave.hpp"
 
 namespace danbo {
 
 constexpr int AV_TR = 64;          // rays per workgroup tile of the view-constant kernels
 constexpr int AV_NK_MAX = 51;      // 3 (1 + 2 L), L <= 8
 constexpr int AV_VW_MAX = 256;
-
-// E[kk], kk = 3 b + axis: b = 0 the unit bone-local ray direction u, b = 1 + 2 l: sin(2^l u), 2 + 2 l: cos(2^l u) -- the values
-// k_anerf_view_pe (k_anerf.hip) writes, in the order of views_linears.0's view columns of ONE joint
-__device__ __forceinline__ void av_ray_pe(const float* __restrict__ rays_d, const float* __restrict__ skts, int R, int G, int L, int ray, int j,
-                                          float* __restrict__ e /* stride 1 */) {
-    const int rays_per_pose = R / G;
-    const float* M = skts + ((size_t)min(ray / rays_per_pose, G - 1) * J + j) * 16;
-    const float d[3] = {rays_d[3 * ray], rays_d[3 * ray + 1], rays_d[3 * ray + 2]};
-    float q[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) q[a] = add_rn(add_rn(mul_rn(M[4 * a], d[0]), mul_rn(M[4 * a + 1], d[1])), mul_rn(M[4 * a + 2], d[2]));
-    const float den = fmaxf(norm3_torch(q[0], q[1], q[2]), 1e-12f);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float u = div_rn(q[k], den);
-        e[k] = u;
-        for (int l = 0; l < L; ++l) {
-            float sn, cs;
-            sincosf(mul_rn(u, (float)(1 << l)), &sn, &cs);
-            e[(1 + 2 * l) * 3 + k] = sn;
-            e[(2 + 2 * l) * 3 + k] = cs;
-        }
-    }
-}
 
 // grid (ray tiles, 24 joints), 256 threads: thread c owns column c of the joint's [nk, VW] weight slice (registers when NK is the
 // compile-time 27 of the shipped multires_views = 4, LDS otherwise); the tile's 64 x nk encodings are LDS broadcasts
@@ -71,7 +47,7 @@ __global__ __launch_bounds__(256) void k_anerf_view_consts(const float* __restri
         const int ray0 = tile * AV_TR;
         if (tid < AV_TR) {
             float* e = s_e + tid * nkp;
-            if (ray0 + tid < R) av_ray_pe(rays_d, skts, R, G, L, ray0 + tid, j, e);
+            if (ray0 + tid < R) av_ray_pe(rays_d, skts, R, G, L, ray0 + tid, j, e, 3);
             else for (int k = 0; k < nk; ++k) e[k] = 0.f;
             for (int k = nk; k < nkp; ++k) e[k] = 0.f;
         }
@@ -132,7 +108,7 @@ __global__ __launch_bounds__(256) void k_anerf_view_consts_bwd(const float* __re
         __syncthreads();
         if (tid < AV_TR) {
             float* e = s_e + tid * nkp;
-            if (ray0 + tid < ray_hi) av_ray_pe(rays_d, skts, R, G, L, ray0 + tid, j, e);
+            if (ray0 + tid < ray_hi) av_ray_pe(rays_d, skts, R, G, L, ray0 + tid, j, e, 3);
             else for (int k = 0; k < nkp; ++k) e[k] = 0.f;
             for (int k = nk; k < nkp; ++k) e[k] = 0.f;
         }
@@ -176,73 +152,16 @@ __global__ __launch_bounds__(256) void k_anerf_view_consts_bwd_reduce(const floa
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
-// colour head, training form (k_anerf.hip k_anerf_color: one wavefront per ray, the ray's 24 x VW joint vectors in registers):
+// colour head, training form (anerf_color_body<true>, anerf_wave.hpp: one wavefront per ray, the ray's 24 x VW joint vectors in
+// registers):
 //   pre_v[c] = featv[row][c] + table_ray[ray][c] + sum_j w[row][j] C[j][ray][c];  hv = relu(pre_v);  raw = (rgb_w hv + rgb_b, alpha[row])
-// rows of the pass: row = rl * S + s (rl = ray - ray0).  hv [rows, VW] is kept for the backward.
+// rows of the pass: row = ray * S + s.  hv [rows, VW] is kept for the backward.
 __global__ __launch_bounds__(256) void k_anerf_color_train(const float* __restrict__ featv, int ldf, const float* __restrict__ w,
                                                            const float* __restrict__ C, const float* __restrict__ table_ray, int R_total,
                                                            int nrays, int S, int VW, const float* __restrict__ rgb_w,
                                                            const float* __restrict__ rgb_b, const float* __restrict__ alpha, int lda,
                                                            float* __restrict__ hv, float* __restrict__ raw_out) {
-    const int lane = threadIdx.x & 63;
-    const int wave_global = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
-    const int nwaves = (gridDim.x * blockDim.x) >> 6;
-    float rw[3][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + 64 * i;
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) rw[ch][i] = c < VW ? rgb_w[ch * VW + c] : 0.f;
-    }
-    const float rb0 = rgb_b[0], rb1 = rgb_b[1], rb2 = rgb_b[2];
-    for (int ray = wave_global; ray < nrays; ray += nwaves) {
-        float cj[J][4], tb[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int c = lane + 64 * i;
-            tb[i] = c < VW ? table_ray[(size_t)ray * VW + c] : 0.f;
-#pragma unroll
-            for (int j = 0; j < J; ++j) cj[j][i] = c < VW ? C[((size_t)j * R_total + ray) * VW + c] : 0.f;
-        }
-        constexpr int U = 4;
-        for (int s0 = 0; s0 < S; s0 += U) {
-            float x[U][4], wj[U][J], al[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const size_t row = (size_t)ray * S + min(s0 + u, S - 1);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int c = lane + 64 * i;
-                    x[u][i] = c < VW ? featv[row * ldf + c] : 0.f;
-                }
-#pragma unroll
-                for (int j = 0; j < J; ++j) wj[u][j] = w[row * J + j];
-                al[u] = alpha[row * lda];
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) x[u][i] = (lane + 64 * i) < VW ? x[u][i] + tb[i] : 0.f;
-#pragma unroll
-                for (int j = 0; j < J; ++j)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) x[u][i] = fmaf(wj[u][j], cj[j][i], x[u][i]);
-                float pr = 0.f, pg = 0.f, pb = 0.f;
-                const size_t row = (size_t)ray * S + s0 + u;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float xr = fmaxf(x[u][i], 0.f);
-                    if (s0 + u < S && lane + 64 * i < VW) hv[row * VW + lane + 64 * i] = xr;
-                    pr = fmaf(xr, rw[0][i], pr);
-                    pg = fmaf(xr, rw[1][i], pg);
-                    pb = fmaf(xr, rw[2][i], pb);
-                }
-                pr = wave_total(pr); pg = wave_total(pg); pb = wave_total(pb);
-                if (lane == 0 && s0 + u < S)
-                    reinterpret_cast<float4*>(raw_out)[row] = make_float4(pr + rb0, pg + rb1, pb + rb2, al[u]);
-            }
-        }
-    }
+    anerf_color_body<true>(featv, ldf, w, C, table_ray, nullptr, 0, R_total, 0, nrays, S, VW, rgb_w, rgb_b, alpha, lda, hv, raw_out);
 }
 
 // power of two that brings `maxabs` to [2^6, 2^7) (1 when maxabs is 0 / not finite); exact both ways
@@ -691,18 +610,6 @@ extern "C" int danbo_anerf_unmerge(const float* d_sorted, const float* d_c0, con
 // ================================================================================================================================
 namespace {
 
-struct ACarver {
-    char* base;
-    size_t used;
-    template <class T>
-    T* take(size_t n) {
-        used = (used + 255) & ~(size_t)255;
-        T* p = base ? reinterpret_cast<T*>(base + used) : nullptr;
-        used += n * sizeof(T);
-        return p;
-    }
-};
-
 constexpr int SIG_TOP = DANBO_ANERF_MAX_D;       // sig / mx slots: [0, D) the trunk layers, [SIG_TOP] d raw / the head
 constexpr int AN_DW_SLICES = 16;
 
@@ -762,12 +669,12 @@ void a_describe_dw(const DanboAnerfTrainModel* m, const ABuffers& b, DanboDwLaye
     *n_layers = k;
 }
 
-ABuffers a_carve(ACarver& c, const AShapes& s, const DanboAnerfTrainModel* m, long dw_floats) {
+ABuffers a_carve(Carver& c, const AShapes& s, const DanboAnerfTrainModel* m, long dw_floats) {
     ABuffers b{};
     const int W = m->W, VW = m->VW, D = m->D, ic = a_in_ch(m), ldh = W + 4;
     const size_t R = (size_t)s.R, Mc = R * s.S, Mf = R * s.Sf, n = Mc + Mf;
     const int nk = 3 * (1 + 2 * m->L_view);
-    c.used = (c.used + 255) & ~(size_t)255;
+    c.align();
     b.zero_begin = c.base ? c.base + c.used : nullptr;
     b.mx = c.take<float>(16);
     b.sig = c.take<float>(16);
@@ -826,7 +733,7 @@ ABuffers a_carve(ACarver& c, const AShapes& s, const DanboAnerfTrainModel* m, lo
 }
 
 long a_dw_floats(const DanboAnerfTrainModel* m, const AShapes& s) {
-    ACarver c0{nullptr, 0};
+    Carver c0;
     ABuffers b0 = a_carve(c0, s, m, 0);
     DanboDwLayer L[DANBO_ANERF_MAX_D + 2];
     int nl = 0;
@@ -838,14 +745,12 @@ bool a_shapes_ok(int R, int G, int S, int Sf, int chunk) {
     return R >= 1 && G >= 1 && R % G == 0 && S >= 3 && Sf >= 1 && S + Sf <= 256 && chunk >= 1 && (long)R * (S + Sf) < (1l << 30);
 }
 
-#define ANERF_TRY(call) do { const int rc_ = (call); if (rc_ != 0) return rc_; } while (0)
-
 }  // namespace
 
 extern "C" size_t danbo_anerf_train_workspace(const DanboAnerfTrainModel* m, int R, int G, int S, int Sf, int chunk) {
     if (!amodel_ok(m) || !a_shapes_ok(R, G, S, Sf, chunk)) return 0;
     AShapes s{R, G, S, Sf, chunk};
-    ACarver c{nullptr, 0};
+    Carver c;
     a_carve(c, s, m, a_dw_floats(m, s));
     return c.used + 512;
 }
@@ -854,7 +759,7 @@ extern "C" int danbo_anerf_train_workspace_view(const DanboAnerfTrainModel* m, i
                                                 DanboTrainView* v) {
     DANBO_CHECK_ARG(amodel_ok(m) && workspace && v && a_shapes_ok(R, G, S, Sf, chunk));
     AShapes s{R, G, S, Sf, chunk};
-    ACarver c{reinterpret_cast<char*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255), 0};
+    Carver c(workspace);
     const ABuffers b = a_carve(c, s, m, 0);
     v->z_coarse = b.z_c; v->z_fine = b.z_f; v->z_sorted = b.z_sorted; v->order = b.order; v->bits_coarse = nullptr; v->bits_fine = nullptr;
     return 0;
@@ -872,7 +777,7 @@ extern "C" int danbo_anerf_train_step(const DanboAnerfTrainModel* m, const Danbo
     DANBO_CHECK_ARG(workspace_bytes >= danbo_anerf_train_workspace(m, R, G, S, Sf, bt->chunk));
     hipStream_t st = (hipStream_t)stream;
     const AShapes sh{R, G, S, Sf, bt->chunk};
-    ACarver c{reinterpret_cast<char*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255), 0};
+    Carver c(workspace);
     const ABuffers b = a_carve(c, sh, m, a_dw_floats(m, sh));
     const int W = m->W, VW = m->VW, D = m->D, ic = a_in_ch(m), ldh = W + 4, ldv = a_ldv(m);
     const int view0 = W, code0 = W + 72 * (1 + 2 * m->L_view);
@@ -882,91 +787,91 @@ extern "C" int danbo_anerf_train_step(const DanboAnerfTrainModel* m, const Danbo
     // ---- zero: running maxima, scales, loss terms; the flat gradient (frame-code rows of cameras that are not in the batch)
     zero_words(b.zero_begin, (long)((b.zero_end - b.zero_begin) / 4), m->g_flat, m->n_flat, st);
     if (bt->rng_state != nullptr)
-        ANERF_TRY(danbo_random_draws(bt->rng_state, (long)bt->n_uniform, bt->rng_uniform, (long)bt->n_normal, bt->normal_std, bt->rng_normal, stream));
+        DANBO_TRY(danbo_random_draws(bt->rng_state, (long)bt->n_uniform, bt->rng_uniform, (long)bt->n_normal, bt->normal_std, bt->rng_normal, stream));
 
     // ---- packing (the weights changed in the last Adam step): every layer in the forward orientation, every layer whose input carries
     //      a gradient in the transposed one; [feature_linear ; alpha_linear] stacked; views_linears.0's view columns per joint
     for (int l = 0; l < D; ++l) {
         const int K = a_k_of(m, l);
         const bool sk = l == m->skip + 1;
-        ANERF_TRY(danbo_linear16_pack(m->pts_w[l], K, 1, W, sk || l == 0 ? ic : W, sk ? W : 0, b.pk_fwd[l], stream));
+        DANBO_TRY(danbo_linear16_pack(m->pts_w[l], K, 1, W, sk || l == 0 ? ic : W, sk ? W : 0, b.pk_fwd[l], stream));
         if (l > 0)      // dY_{l-1} = dz_l W_l[:, columns of y_{l-1}]:  (W_l^T)[n', k'] = W_l[k', col + n']
-            ANERF_TRY(danbo_linear16_pack(m->pts_w[l] + (sk ? ic : 0), 1, K, W, W, 0, b.pk_bwd[l], stream));
+            DANBO_TRY(danbo_linear16_pack(m->pts_w[l] + (sk ? ic : 0), 1, K, W, W, 0, b.pk_bwd[l], stream));
     }
     hipLaunchKernelGGL(k_anerf_stack_head, dim3(stream_grid((long)(W + 1) * W, 256)), dim3(256), 0, st, m->feature_w, m->feature_b, m->alpha_w,
                        m->alpha_b, W, W, b.wstack, b.bstack);
-    ANERF_TRY(danbo_linear16_pack(b.wstack, W, 1, W + 1, W, 0, b.pk_head, stream));
-    ANERF_TRY(danbo_linear16_pack(b.wstack, 1, W, W, W + 1, 0, b.pk_head_t, stream));
-    ANERF_TRY(danbo_linear16_pack(m->views_w, ldv, 1, VW, W, 0, b.pk_featv, stream));
-    ANERF_TRY(danbo_linear16_pack(m->views_w, 1, ldv, W, VW, 0, b.pk_featv_t, stream));
-    ANERF_TRY(danbo_anerf_view_wj_pack(m->views_w, ldv, view0, VW, m->L_view, b.wj, stream));
+    DANBO_TRY(danbo_linear16_pack(b.wstack, W, 1, W + 1, W, 0, b.pk_head, stream));
+    DANBO_TRY(danbo_linear16_pack(b.wstack, 1, W, W, W + 1, 0, b.pk_head_t, stream));
+    DANBO_TRY(danbo_linear16_pack(m->views_w, ldv, 1, VW, W, 0, b.pk_featv, stream));
+    DANBO_TRY(danbo_linear16_pack(m->views_w, 1, ldv, W, VW, 0, b.pk_featv_t, stream));
+    DANBO_TRY(danbo_anerf_view_wj_pack(m->views_w, ldv, view0, VW, m->L_view, b.wj, stream));
 
     // ---- per ray: bounds, stratified depths, view constants, bias + frame-code rows
-    ANERF_TRY(danbo_near_far_cylinder(bt->rays_o, bt->rays_d, bt->cyls, R, G, 0.f, 1.f, bt->near_in, bt->far_in, bt->chunk, b.cyl_scratch, b.near,
+    DANBO_TRY(danbo_near_far_cylinder(bt->rays_o, bt->rays_d, bt->cyls, R, G, 0.f, 1.f, bt->near_in, bt->far_in, bt->chunk, b.cyl_scratch, b.near,
                                       b.far, stream));
-    ANERF_TRY(danbo_coarse_samples(b.near, b.far, R, S, bt->t_rand, b.z_c, stream));
-    ANERF_TRY(danbo_anerf_view_consts_fwd(bt->rays_d, bt->skts, R, G, m->L_view, b.wj, VW, b.C, stream));
-    ANERF_TRY(danbo_anerf_ray_table(m->views_w, ldv, code0, m->code_size, m->views_b, m->codes, m->n_codes, bt->cam_idx, R, VW, b.table_ray, stream));
+    DANBO_TRY(danbo_coarse_samples(b.near, b.far, R, S, bt->t_rand, b.z_c, stream));
+    DANBO_TRY(danbo_anerf_view_consts_fwd(bt->rays_d, bt->skts, R, G, m->L_view, b.wj, VW, b.C, stream));
+    DANBO_TRY(danbo_anerf_ray_table(m->views_w, ldv, code0, m->code_size, m->views_b, m->codes, m->n_codes, bt->cam_idx, R, VW, b.table_ray, stream));
 
     // ---- one network pass over the rows [r0, r0 + np) = the R x s samples at depths zz
     auto network = [&](const float* zz, int s, long r0, float* raw) -> int {
         const int np = (int)((long)R * s);
         float* x0 = b.x0 + r0 * ic;
-        ANERF_TRY(danbo_anerf_encode_fwd_dtau(bt->rays_o, bt->rays_d, zz, nullptr, R, s, G, bt->skts, m->align, m->cutoff, m->tau, m->L, 0, np, x0,
+        DANBO_TRY(danbo_anerf_encode_fwd_dtau(bt->rays_o, bt->rays_d, zz, nullptr, R, s, G, bt->skts, m->align, m->cutoff, m->tau, m->L, 0, np, x0,
                                               b.wcut + r0 * J, stream));
         for (int l = 0; l < D; ++l) {
             float* y = b.y[l] + r0 * W;
-            if (l == 0) ANERF_TRY(danbo_linear16_fwd(x0, ic, ic, nullptr, 0, 0, b.pk_fwd[l], m->pts_b[l], W, 1, y, W, np, nullptr, stream));
+            if (l == 0) DANBO_TRY(danbo_linear16_fwd(x0, ic, ic, nullptr, 0, 0, b.pk_fwd[l], m->pts_b[l], W, 1, y, W, np, nullptr, stream));
             else if (l == m->skip + 1)
-                ANERF_TRY(danbo_linear16_fwd(x0, ic, ic, b.y[l - 1] + r0 * W, W, W, b.pk_fwd[l], m->pts_b[l], W, 1, y, W, np, nullptr, stream));
-            else ANERF_TRY(danbo_linear16_fwd(b.y[l - 1] + r0 * W, W, W, nullptr, 0, 0, b.pk_fwd[l], m->pts_b[l], W, 1, y, W, np, nullptr, stream));
+                DANBO_TRY(danbo_linear16_fwd(x0, ic, ic, b.y[l - 1] + r0 * W, W, W, b.pk_fwd[l], m->pts_b[l], W, 1, y, W, np, nullptr, stream));
+            else DANBO_TRY(danbo_linear16_fwd(b.y[l - 1] + r0 * W, W, W, nullptr, 0, 0, b.pk_fwd[l], m->pts_b[l], W, 1, y, W, np, nullptr, stream));
         }
         float* head = b.head + r0 * ldh;
-        ANERF_TRY(danbo_linear16_fwd(b.y[D - 1] + r0 * W, W, W, nullptr, 0, 0, b.pk_head, b.bstack, W + 1, 0, head, ldh, np, nullptr, stream));
-        ANERF_TRY(danbo_linear16_fwd(head, ldh, W, nullptr, 0, 0, b.pk_featv, nullptr, VW, 0, b.featv + r0 * VW, VW, np, nullptr, stream));
+        DANBO_TRY(danbo_linear16_fwd(b.y[D - 1] + r0 * W, W, W, nullptr, 0, 0, b.pk_head, b.bstack, W + 1, 0, head, ldh, np, nullptr, stream));
+        DANBO_TRY(danbo_linear16_fwd(head, ldh, W, nullptr, 0, 0, b.pk_featv, nullptr, VW, 0, b.featv + r0 * VW, VW, np, nullptr, stream));
         return danbo_anerf_color_train_fwd(b.featv + r0 * VW, VW, b.wcut + r0 * J, b.C, b.table_ray, R, R, s, VW, m->rgb_w, m->rgb_b, head + W, ldh,
                                            b.hv + r0 * VW, raw, stream);
     };
-    ANERF_TRY(network(b.z_c, S, 0, b.raw_c));
-    ANERF_TRY(danbo_composite_fwd(b.raw_c, b.z_c, bt->rays_d, R, S, B, bt->noise_c, o->rgb0, o->disp0, o->acc0, b.weights0, o->alpha0, stream));
-    ANERF_TRY(danbo_importance_samples(b.z_c, b.weights0, R, S, Sf, bt->u_rand, b.z_f, b.z_sorted, b.order, stream));
-    ANERF_TRY(network(b.z_f, Sf, Mc, b.raw_f));
-    ANERF_TRY(danbo_merge_samples(b.raw_c, b.raw_f, b.order, R, S, Sf, 4, b.raw_sorted, stream));
-    ANERF_TRY(danbo_composite_fwd(b.raw_sorted, b.z_sorted, bt->rays_d, R, S + Sf, B, bt->noise_f, o->rgb_map, o->disp_map, o->acc_map, o->weights,
+    DANBO_TRY(network(b.z_c, S, 0, b.raw_c));
+    DANBO_TRY(danbo_composite_fwd(b.raw_c, b.z_c, bt->rays_d, R, S, B, bt->noise_c, o->rgb0, o->disp0, o->acc0, b.weights0, o->alpha0, stream));
+    DANBO_TRY(danbo_importance_samples(b.z_c, b.weights0, R, S, Sf, bt->u_rand, b.z_f, b.z_sorted, b.order, stream));
+    DANBO_TRY(network(b.z_f, Sf, Mc, b.raw_f));
+    DANBO_TRY(danbo_merge_samples(b.raw_c, b.raw_f, b.order, R, S, Sf, 4, b.raw_sorted, stream));
+    DANBO_TRY(danbo_composite_fwd(b.raw_sorted, b.z_sorted, bt->rays_d, R, S + Sf, B, bt->noise_f, o->rgb_map, o->disp_map, o->acc_map, o->weights,
                                   o->alpha, stream));
 
     // ---- losses (trainer.py:396-422), the adjoints of the two composites, the un-merge
-    ANERF_TRY(danbo_train_loss_grad(o->rgb_map, o->acc_map, o->rgb0, o->acc0, bt->target, bt->bgs, m->use_background, R, m->loss_mse, m->rgb_loss_coef,
+    DANBO_TRY(danbo_train_loss_grad(o->rgb_map, o->acc_map, o->rgb0, o->acc0, bt->target, bt->bgs, m->use_background, R, m->loss_mse, m->rgb_loss_coef,
                                     m->rgb_loss_coef * m->coarse_weight, b.g_rgb, b.g_acc, b.g_rgb0, b.g_acc0, b.loss, stream));
-    ANERF_TRY(danbo_composite_bwd(b.raw_c, b.z_c, bt->rays_d, R, S, B, bt->noise_c, b.g_rgb0, b.g_acc0, b.d_c0, stream));
-    ANERF_TRY(danbo_composite_bwd(b.raw_sorted, b.z_sorted, bt->rays_d, R, S + Sf, B, bt->noise_f, b.g_rgb, b.g_acc, b.d_sorted, stream));
-    ANERF_TRY(danbo_anerf_unmerge(b.d_sorted, b.d_c0, b.order, R, S, Sf, b.d_all, b.mx + SIG_TOP, stream));
+    DANBO_TRY(danbo_composite_bwd(b.raw_c, b.z_c, bt->rays_d, R, S, B, bt->noise_c, b.g_rgb0, b.g_acc0, b.d_c0, stream));
+    DANBO_TRY(danbo_composite_bwd(b.raw_sorted, b.z_sorted, bt->rays_d, R, S + Sf, B, bt->noise_f, b.g_rgb, b.g_acc, b.d_sorted, stream));
+    DANBO_TRY(danbo_anerf_unmerge(b.d_sorted, b.d_c0, b.order, R, S, Sf, b.d_all, b.mx + SIG_TOP, stream));
 
     // ---- colour head and view branch
-    ANERF_TRY(danbo_anerf_color_bwd(b.d_all, b.hv, b.wcut, R, R, S, VW, m->rgb_w, b.mx + SIG_TOP, b.sig + SIG_TOP, b.d_featv, b.d_head + W, ldh, b.dC,
+    DANBO_TRY(danbo_anerf_color_bwd(b.d_all, b.hv, b.wcut, R, R, S, VW, m->rgb_w, b.mx + SIG_TOP, b.sig + SIG_TOP, b.d_featv, b.d_head + W, ldh, b.dC,
                                     b.d_pre_ray, 0, b.part, stream));
-    ANERF_TRY(danbo_anerf_color_bwd(b.d_all + Mc * 4, b.hv + Mc * VW, b.wcut + Mc * J, R, R, Sf, VW, m->rgb_w, b.mx + SIG_TOP, b.sig + SIG_TOP,
+    DANBO_TRY(danbo_anerf_color_bwd(b.d_all + Mc * 4, b.hv + Mc * VW, b.wcut + Mc * J, R, R, Sf, VW, m->rgb_w, b.mx + SIG_TOP, b.sig + SIG_TOP,
                                     b.d_featv + Mc * VW, b.d_head + Mc * ldh + W, ldh, b.dC, b.d_pre_ray, 1, b.part + b.part_floats_c, stream));
-    ANERF_TRY(danbo_anerf_rgb_reduce(b.part, b.part_floats_c + b.part_floats_f, VW, m->g_rgb_w, m->g_rgb_b, stream));
-    ANERF_TRY(danbo_anerf_view_consts_bwd(bt->rays_d, bt->skts, R, G, m->L_view, b.dC, VW, m->g_views_w, ldv, view0, b.vc_scratch, stream));
-    ANERF_TRY(danbo_anerf_code_grads(b.d_pre_ray, m->views_w, ldv, code0, m->code_size, m->codes, m->n_codes, bt->cam_idx, R, VW, m->g_views_w,
+    DANBO_TRY(danbo_anerf_rgb_reduce(b.part, b.part_floats_c + b.part_floats_f, VW, m->g_rgb_w, m->g_rgb_b, stream));
+    DANBO_TRY(danbo_anerf_view_consts_bwd(bt->rays_d, bt->skts, R, G, m->L_view, b.dC, VW, m->g_views_w, ldv, view0, b.vc_scratch, stream));
+    DANBO_TRY(danbo_anerf_code_grads(b.d_pre_ray, m->views_w, ldv, code0, m->code_size, m->codes, m->n_codes, bt->cam_idx, R, VW, m->g_views_w,
                                      m->g_views_b, m->code_size > 0 ? m->g_codes : nullptr, b.code_v, stream));
 
     // ---- the input-gradient chain: d feature = d featv W_v[:, :W] -> dY_{D-1} = [d feature | d alpha] [W_f ; w_alpha] -> the trunk
-    ANERF_TRY(danbo_linear16_fwd(b.d_featv, VW, VW, nullptr, 0, 0, b.pk_featv_t, nullptr, W, 0, b.d_head, ldh, (int)n, nullptr, stream));
-    ANERF_TRY(danbo_linear16_fwd(b.d_head, ldh, W + 1, nullptr, 0, 0, b.pk_head_t, nullptr, W, 0, b.t, W, (int)n, nullptr, stream));
+    DANBO_TRY(danbo_linear16_fwd(b.d_featv, VW, VW, nullptr, 0, 0, b.pk_featv_t, nullptr, W, 0, b.d_head, ldh, (int)n, nullptr, stream));
+    DANBO_TRY(danbo_linear16_fwd(b.d_head, ldh, W + 1, nullptr, 0, 0, b.pk_head_t, nullptr, W, 0, b.t, W, (int)n, nullptr, stream));
     for (int l = D - 1; l >= 0; --l) {
         const bool top = l == D - 1;
-        ANERF_TRY(danbo_anerf_relu_mask(b.t, b.y[l], n * W, top ? nullptr : b.mx + l + 1, b.sig + (top ? SIG_TOP : l + 1), b.sig + l, b.mx + l, b.dz[l],
+        DANBO_TRY(danbo_anerf_relu_mask(b.t, b.y[l], n * W, top ? nullptr : b.mx + l + 1, b.sig + (top ? SIG_TOP : l + 1), b.sig + l, b.mx + l, b.dz[l],
                                         stream));
-        if (l > 0) ANERF_TRY(danbo_linear16_fwd(b.dz[l], W, W, nullptr, 0, 0, b.pk_bwd[l], nullptr, W, 0, b.t, W, (int)n, nullptr, stream));
+        if (l > 0) DANBO_TRY(danbo_linear16_fwd(b.dz[l], W, W, nullptr, 0, 0, b.pk_bwd[l], nullptr, W, 0, b.t, W, (int)n, nullptr, stream));
     }
 
     // ---- all weight / bias gradients of the dense layers in one launch, then the powers of two divided out
     DanboDwLayer dwl[DANBO_ANERF_MAX_D + 2];
     int n_dw = 0;
     a_describe_dw(m, b, dwl, &n_dw);
-    ANERF_TRY(danbo_dw16(dwl, n_dw, (int)n, nullptr, AN_DW_SLICES, b.dw_scratch, stream));
+    DANBO_TRY(danbo_dw16(dwl, n_dw, (int)n, nullptr, AN_DW_SLICES, b.dw_scratch, stream));
     AnerfSegs segs{};
     auto seg = [&](float* p, int rows, int cols, int ld, int sig) { segs.s[segs.n++] = AnerfSeg{p, rows, cols, ld, sig}; };
     for (int l = 0; l < D; ++l) {

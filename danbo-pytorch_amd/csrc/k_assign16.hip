@@ -16,9 +16,6 @@
 
 namespace danbo {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int A16_CHUNK = 32768;
 constexpr int A16_NCHUNK = 8;  // 236 pieces of 1 KB, padded to 256
 static_assert(A16_NCHUNK * A16_CHUNK == DANBO_ASSIGN16_PACKED_BYTES, "header constant out of date");

@@ -28,9 +28,7 @@
 
 namespace danbo {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ half8 dw_frag(const char* p) {   // 16 bytes at an 8-byte aligned LDS address

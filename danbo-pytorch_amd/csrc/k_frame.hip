@@ -9,18 +9,6 @@
 using namespace danbo;
 
 namespace {
-struct Carver {
-    char* base;
-    size_t used, cap;
-    template <class T>
-    T* take(size_t n) {
-        used = (used + 255) & ~(size_t)255;
-        T* p = base ? reinterpret_cast<T*>(base + used) : nullptr;
-        used += n * sizeof(T);
-        return p;
-    }
-};
-
 struct FrameBuffers {
     float *near, *far, *cyl_scratch, *z, *vol_scratch, *volumes, *cview, *raw_empty, *h, *raw_a, *raw_b, *z_fine, *z_sorted, *weights0;
     uint32_t *bits_a, *bits_b, *ray_mask, *ray_flat;
@@ -59,12 +47,10 @@ FrameBuffers carve(Carver& c, int R, int G, int S, int Sf, int chunk, int Wg) {
 
 extern "C" size_t danbo_render_frame_workspace(int R, int G, int S, int Sf, int chunk, int graph_width) {
     if (R < 1 || G < 1 || S < 1 || Sf < 1 || chunk < 1 || graph_width < 1) return 0;
-    Carver c{nullptr, 0, 0};
+    Carver c;
     carve(c, R, G, S, Sf, chunk, graph_width);
     return c.used + 256;
 }
-
-#define DANBO_TRY(call) do { const int rc_ = (call); if (rc_ != 0) return rc_; } while (0)
 
 // act / shift: the density activation of the three composites (danbo_hip.h).  Softplus: no rays of constants, whatever the
 // model says -- the density of empty space is positive on every sample, so every ray is evaluated
@@ -77,7 +63,7 @@ static int render_frame_impl(const DanboModel* m, const DanboRays* r, int S, int
     const int R = r->R, G = r->G;
     const bool flat_rays = m->flat_rays_ok != 0 && act == DANBO_DENSITY_RELU;
     DANBO_CHECK_ARG(workspace_bytes >= danbo_render_frame_workspace(R, G, S, Sf, r->chunk, m->graph_width));
-    Carver c{reinterpret_cast<char*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255), 0, workspace_bytes};
+    Carver c(workspace);
     const FrameBuffers b = carve(c, R, G, S, Sf, r->chunk, m->graph_width);
     hipStream_t st = (hipStream_t)stream;
 

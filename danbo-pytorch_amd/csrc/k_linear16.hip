@@ -30,9 +30,6 @@
 
 namespace danbo {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int L16_CHUNK = 32768, L16_SLOTS = 4, L16_BM = 128, L16_THREADS = 512, L16_MAX_N = 512;
 constexpr int L16_LDS_BYTES = L16_SLOTS * L16_CHUNK + L16_MAX_N * 4;
 constexpr int L16_COLOR_LD = 256, L16_COLOR_LDS_BYTES = L16_LDS_BYTES + 3 * L16_COLOR_LD * 4;   // + rgb_linear.weight for the colour epilogue

@@ -17,8 +17,6 @@
 
 namespace danbo {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int MLP_BM = 64;
 constexpr int MLP_W = 256;
 constexpr int MLP_VW = 128;
@@ -196,6 +194,7 @@ __global__ __launch_bounds__(256) void k_view_consts(const float* __restrict__ r
             float d[3] = {rays_d[3 * r], rays_d[3 * r + 1], rays_d[3 * r + 2]};
             if (ray_mode == 1) {
                 const float* M = skts + (size_t)min(r / rays_per_pose, G - 1) * J * 16;  // bone 0 = root
+                // rotate_unfused / normalize3 of sample_math.hpp, restated: the calls moved this kernel's assembly, and it is on the frame's path
                 float t[3];
                 for (int a = 0; a < 3; ++a)
                     t[a] = add_rn(add_rn(mul_rn(M[4 * a], d[0]), mul_rn(M[4 * a + 1], d[1])), mul_rn(M[4 * a + 2], d[2]));

@@ -30,8 +30,6 @@
 
 namespace danbo {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int M32_THREADS = 256;
 constexpr int M32_NCH = 74;
 constexpr int M32_W = 256, M32_VW = 128;
@@ -429,7 +427,6 @@ __device__ __forceinline__ void pe_slot(const float (&hv)[8], PeJob& j, PeFrag& 
     } else if constexpr (M == 21) {
         M32_SPLIT_PAIR(2) M32_SPLIT_PAIR(3)
 #undef M32_SPLIT_PAIR
-        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
         xh = __builtin_bit_cast(half8, u32x4{f.h[0], f.h[1], f.h[2], f.h[3]});
         xl = __builtin_bit_cast(half8, u32x4{f.l[0], f.l[1], f.l[2], f.l[3]});
     }

@@ -693,9 +693,8 @@ __global__ __launch_bounds__(GATHER_BLOCK) void k_bone_gather(const float* __res
         // coalesced 16-B stores of the 16 x 1440 B tile
         const int rows_here = min(GATHER_TS, n - row0);
         const int nvec = rows_here * (J * FEAT / 4);
-        typedef float f32x4_t __attribute__((ext_vector_type(4)));
-        f32x4_t* dst = reinterpret_cast<f32x4_t*>(part_feat + (size_t)row0 * J * FEAT);
-        const f32x4_t* src = reinterpret_cast<const f32x4_t*>(s_out);
+        f32x4* dst = reinterpret_cast<f32x4*>(part_feat + (size_t)row0 * J * FEAT);
+        const f32x4* src = reinterpret_cast<const f32x4*>(s_out);
         // write-once stream: non-temporal, it is 1 440 B per sample and must not evict the volumes / transforms
         for (int i = tid; i < nvec; i += GATHER_BLOCK) __builtin_nontemporal_store(src[i], dst + i);
     }
@@ -764,9 +763,9 @@ __device__ __forceinline__ float composite_chunk(CompositeState& st, const float
     const float T = mul_rn(st.carry, excl);
     st.carry = mul_rn(st.carry, __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, p), 63)));
     const float w = mul_rn(al, T);
-    const float cr = sub_rn(mul_rn(sigmoidf_(rw.x), 1.002f), 0.001f);
-    const float cg = sub_rn(mul_rn(sigmoidf_(rw.y), 1.002f), 0.001f);
-    const float cb = sub_rn(mul_rn(sigmoidf_(rw.z), 1.002f), 0.001f);
+    const float cr = rgb_of_logit(rw.x);
+    const float cg = rgb_of_logit(rw.y);
+    const float cb = rgb_of_logit(rw.z);
     st.sr += wave_total(w * cr);
     st.sg += wave_total(w * cg);
     st.sb += wave_total(w * cb);
@@ -780,9 +779,7 @@ __device__ __forceinline__ void composite_finish(const CompositeState& st, int r
     rgb_map[3 * r] = st.sr;
     rgb_map[3 * r + 1] = st.sg;
     rgb_map[3 * r + 2] = st.sb;
-    float dsp = div_rn(1.0f, fmaxf(1e-10f, div_rn(st.sd, add_rn(st.sa, 1e-10f))));
-    if (fabsf(st.sa) <= 1e-8f) dsp = 0.f;
-    disp[r] = dsp;
+    disp[r] = disp_of(st.sd, st.sa);
     acc_out[r] = fminf(st.sa, 1.0f);
 }
 
@@ -883,14 +880,14 @@ __global__ __launch_bounds__(64) void k_importance(const float* __restrict__ z, 
             for (int i = 0; i < S; ++i) {
                 int rank = 0;
                 for (int k = 0; k < Sf; ++k) rank += zf[k] < zr[i];
-                for (int q = 0; q < S; ++q) rank += (zr[q] < zr[i]) || (zr[q] == zr[i] && q < i);
+                for (int q = 0; q < S; ++q) rank += sorts_before(zr[q], q, zr[i], i);
                 zs[rank] = zr[i];
                 si[rank] = i;
             }
             for (int k = 0; k < Sf; ++k) {
                 int rank = 0;
                 for (int i = 0; i < S; ++i) rank += zr[i] <= zf[k];
-                for (int q = 0; q < Sf; ++q) rank += (zf[q] < zf[k]) || (zf[q] == zf[k] && q < k);
+                for (int q = 0; q < Sf; ++q) rank += sorts_before(zf[q], q, zf[k], k);
                 zs[rank] = zf[k];
                 si[rank] = S + k;
             }
@@ -930,10 +927,10 @@ __device__ __forceinline__ void importance_wave(float zi, float wi, int r, int S
             if (cm > uk) hi = mid; else lo = mid + 1;
         }
     }
-    const int below = lo - 1 > 0 ? lo - 1 : 0;
-    const int above = lo < ncdf - 1 ? lo : ncdf - 1;
+    const int below = cdf_below(lo), above = cdf_above(lo, ncdf);
     const float c0 = __shfl(cdf, below, 64), c1 = __shfl(cdf, above, 64);
     const float b0 = __shfl(bin, below, 64), b1 = __shfl(bin, above, 64);
+    // inverse_cdf_point of sample_math.hpp, restated: the call moved this kernel's registers and schedule
     float denom = sub_rn(c1, c0);
     if (denom < 1e-5f) denom = 1.0f;
     const float t = div_rn(sub_rn(uk, c0), denom);
@@ -965,13 +962,13 @@ __device__ __forceinline__ void importance_wave(float zi, float wi, int r, int S
         for (int k = 0; k < Sf; ++k) {
             const float zk = __shfl(zf, k, 64);
             rank_c += zk < zi;
-            rank_f += (zk < zf) || (zk == zf && k < lane);
+            rank_f += sorts_before(zk, k, zf, lane);
         }
         if (ascending) rank_c += lane;
         for (int i = 0; i < S; ++i) {
             const float zc = __shfl(zi, i, 64);
             rank_f += zc <= zf;
-            if (!ascending) rank_c += (zc < zi) || (zc == zi && i < lane);
+            if (!ascending) rank_c += sorts_before(zc, i, zi, lane);
         }
     }
     const size_t o = (size_t)r * (S + Sf);
@@ -1071,10 +1068,10 @@ __global__ __launch_bounds__(256) void k_importance_wave_long(const float* __res
                 if (cm > uk) hi = mid; else lo = mid + 1;
             }
         }
-        const int below = lo - 1 > 0 ? lo - 1 : 0;
-        const int above = lo < ncdf - 1 ? lo : ncdf - 1;
+        const int below = cdf_below(lo), above = cdf_above(lo, ncdf);
         const float c0 = s_w[below], c1 = s_w[above];
         const float b0 = s_b[below], b1 = s_b[above];
+        // inverse_cdf_point of sample_math.hpp, restated: the call moved this kernel's registers and schedule
         float denom = sub_rn(c1, c0);
         if (denom < 1e-5f) denom = 1.0f;
         const float t = div_rn(sub_rn(uk, c0), denom);
@@ -1107,6 +1104,7 @@ __global__ __launch_bounds__(256) void k_importance_wave_long(const float* __res
             }
         } else {
             // general case: rank = number of predecessors in (value, coarse-before-fine, index) order
+            // (the rank rule twice below: sorts_before of sample_math.hpp, restated -- the calls moved this kernel's assembly)
             int rank_f = 0;
             for (int k = 0; k < Sf; ++k) {
                 const float zk = s_f[k];
@@ -1401,111 +1399,128 @@ extern "C" int danbo_merge_samples(const float* a, const float* b, const int32_t
     DANBO_LAUNCH_RET();
 }
 
+// The entry points of a family are one-line calls of its most general one, which holds the argument checks and the dispatch
+// over the kernel's template parameters; what is dispatched on an unchanged argument list takes it as one aggregate.
+struct CompositeArgs {
+    const float *raw, *raw_empty;
+    const uint32_t* bits;
+    const float *z, *rays_d;
+    int R, S;
+    float B;
+    const float* noise;
+    float *rgb_map, *disp, *acc, *weights, *alpha;
+    const int32_t *ray_list, *ray_count;
+};
 template <int DA>
-static int composite_impl(const float* raw, const float* raw_empty, const uint32_t* bits, const float* z, const float* rays_d, int R,
-                          int S, float B, const float* noise, float* rgb_map, float* disp, float* acc, float* weights, float* alpha,
-                          const int32_t* ray_list, const int32_t* ray_count, float shift, void* stream) {
-    DANBO_CHECK_ARG(R > 0 && S > 0 && B > 0.f);
-    DANBO_CHECK_ARG((ray_list == nullptr) == (ray_count == nullptr) && (bits == nullptr || raw_empty != nullptr));
+static int composite_launch(const CompositeArgs& a, float shift, void* stream) {
     static const int per_launch = resident_grid(k_composite<DA>, 1L << 40, 256);
-    const int grid = (int)std::min<long>(ceil_div((long)R * 64, 256), per_launch);
-    hipLaunchKernelGGL(k_composite<DA>, dim3(grid), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float4*>(raw),
-                       reinterpret_cast<const float4*>(raw_empty), bits, z, rays_d, R, S, B, shift, noise, rgb_map, disp, acc, weights,
-                       alpha, ray_list, ray_count);
+    const int grid = (int)std::min<long>(ceil_div((long)a.R * 64, 256), per_launch);
+    hipLaunchKernelGGL(k_composite<DA>, dim3(grid), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float4*>(a.raw),
+                       reinterpret_cast<const float4*>(a.raw_empty), a.bits, a.z, a.rays_d, a.R, a.S, a.B, shift, a.noise, a.rgb_map, a.disp,
+                       a.acc, a.weights, a.alpha, a.ray_list, a.ray_count);
     DANBO_LAUNCH_RET();
 }
 extern "C" int danbo_composite_fwd(const float* raw, const float* z, const float* rays_d, int R, int S, float B,
                                     const float* noise, float* rgb_map, float* disp, float* acc, float* weights,
                                     float* alpha, void* stream) {
-    return composite_impl<DENSITY_RELU>(raw, nullptr, nullptr, z, rays_d, R, S, B, noise, rgb_map, disp, acc, weights, alpha, nullptr,
-                                        nullptr, 0.f, stream);
+    return danbo_composite_rays_fwd(raw, nullptr, nullptr, z, rays_d, R, S, B, noise, rgb_map, disp, acc, weights, alpha, nullptr, nullptr, stream);
 }
 extern "C" int danbo_composite_rays_fwd(const float* raw, const float* raw_empty, const uint32_t* valid_bits, const float* z,
                                          const float* rays_d, int R, int S, float B, const float* noise, float* rgb_map,
                                          float* disp, float* acc, float* weights, float* alpha, const int32_t* ray_list,
                                          const int32_t* ray_count, void* stream) {
-    return composite_impl<DENSITY_RELU>(raw, raw_empty, valid_bits, z, rays_d, R, S, B, noise, rgb_map, disp, acc, weights, alpha, ray_list,
-                                        ray_count, 0.f, stream);
+    return danbo_composite_rays_fwd_act(raw, raw_empty, valid_bits, z, rays_d, R, S, B, noise, rgb_map, disp, acc, weights, alpha, ray_list,
+                                        ray_count, DENSITY_RELU, 0.f, stream);
 }
 extern "C" int danbo_composite_rays_fwd_act(const float* raw, const float* raw_empty, const uint32_t* valid_bits, const float* z,
                                              const float* rays_d, int R, int S, float B, const float* noise, float* rgb_map,
                                              float* disp, float* acc, float* weights, float* alpha, const int32_t* ray_list,
                                              const int32_t* ray_count, int act, float shift, void* stream) {
     DANBO_CHECK_DENSITY_ACT(act, shift);
-    return act == DENSITY_SOFTPLUS
-               ? composite_impl<DENSITY_SOFTPLUS>(raw, raw_empty, valid_bits, z, rays_d, R, S, B, noise, rgb_map, disp, acc, weights, alpha,
-                                                  ray_list, ray_count, shift, stream)
-               : composite_impl<DENSITY_RELU>(raw, raw_empty, valid_bits, z, rays_d, R, S, B, noise, rgb_map, disp, acc, weights, alpha,
-                                              ray_list, ray_count, 0.f, stream);
+    DANBO_CHECK_ARG(R > 0 && S > 0 && B > 0.f);
+    DANBO_CHECK_ARG((ray_list == nullptr) == (ray_count == nullptr) && (valid_bits == nullptr || raw_empty != nullptr));
+    const CompositeArgs a{raw, raw_empty, valid_bits, z, rays_d, R, S, B, noise, rgb_map, disp, acc, weights, alpha, ray_list, ray_count};
+    return act == DENSITY_SOFTPLUS ? composite_launch<DENSITY_SOFTPLUS>(a, shift, stream) : composite_launch<DENSITY_RELU>(a, 0.f, stream);
 }
 
+struct ImportanceArgs {
+    const float *z, *weights;
+    int R, S, Sf;
+    const float* u;
+    float *z_fine, *z_sorted;
+    int32_t* sorted_idx;
+    const int32_t *ray_list, *ray_count;
+};
 template <bool TWO>
-static int importance_impl(const float* z, const float* weights, int R, int S, int Sf, const float* u, float* z_fine,
-                           float* z_sorted, int32_t* sorted_idx, const int32_t* ray_list, const int32_t* ray_count, void* stream) {
-    DANBO_CHECK_ARG(R > 0 && S >= 3 && Sf > 0);
-    DANBO_CHECK_ARG((ray_list == nullptr) == (ray_count == nullptr));
-    DANBO_CHECK_ARG(ray_list == nullptr || (S > 64 && S <= IMPB_MAX_S && Sf <= 64));      // (the list: the long-ray kernel only)
+static int importance_launch(const ImportanceArgs& a, void* stream) {
+    const int R = a.R, S = a.S, Sf = a.Sf;
     if (S <= 64 && Sf <= 64) {
-        if (u)
+        if (a.u)
             hipLaunchKernelGGL((k_importance_wave<false, TWO>), dim3(stream_grid((long)R * 64, 256)), dim3(256), 0,
-                               (hipStream_t)stream, z, weights, R, S, Sf, u, z_fine, z_sorted, sorted_idx);
+                               (hipStream_t)stream, a.z, a.weights, R, S, Sf, a.u, a.z_fine, a.z_sorted, a.sorted_idx);
         else
             hipLaunchKernelGGL((k_importance_wave<true, TWO>), dim3(stream_grid((long)R * 64, 256)), dim3(256), 0,
-                               (hipStream_t)stream, z, weights, R, S, Sf, u, z_fine, z_sorted, sorted_idx);
+                               (hipStream_t)stream, a.z, a.weights, R, S, Sf, a.u, a.z_fine, a.z_sorted, a.sorted_idx);
     } else if (S <= IMPB_MAX_S && Sf <= 64) {
         const dim3 grid(stream_grid((long)R * 64, 256));
-        if (u)
-            hipLaunchKernelGGL((k_importance_wave_long<false, TWO>), grid, dim3(256), 0, (hipStream_t)stream, z, weights, R, S, Sf, u, z_fine,
-                               z_sorted, sorted_idx, ray_scatter(R), ray_list, ray_count);
+        if (a.u)
+            hipLaunchKernelGGL((k_importance_wave_long<false, TWO>), grid, dim3(256), 0, (hipStream_t)stream, a.z, a.weights, R, S, Sf, a.u,
+                               a.z_fine, a.z_sorted, a.sorted_idx, ray_scatter(R), a.ray_list, a.ray_count);
         else
-            hipLaunchKernelGGL((k_importance_wave_long<true, TWO>), grid, dim3(256), 0, (hipStream_t)stream, z, weights, R, S, Sf, u, z_fine,
-                               z_sorted, sorted_idx, ray_scatter(R), ray_list, ray_count);
+            hipLaunchKernelGGL((k_importance_wave_long<true, TWO>), grid, dim3(256), 0, (hipStream_t)stream, a.z, a.weights, R, S, Sf, a.u,
+                               a.z_fine, a.z_sorted, a.sorted_idx, ray_scatter(R), a.ray_list, a.ray_count);
     } else {
-        hipLaunchKernelGGL(k_importance<TWO>, dim3(stream_grid(R, 64)), dim3(64), 0, (hipStream_t)stream, z, weights, R, S, Sf,
-                           u, z_fine, z_sorted, sorted_idx);
+        hipLaunchKernelGGL(k_importance<TWO>, dim3(stream_grid(R, 64)), dim3(64), 0, (hipStream_t)stream, a.z, a.weights, R, S, Sf,
+                           a.u, a.z_fine, a.z_sorted, a.sorted_idx);
     }
     DANBO_LAUNCH_RET();
 }
 extern "C" int danbo_importance_samples(const float* z, const float* weights, int R, int S, int Sf, const float* u,
                                          float* z_fine, float* z_sorted, int32_t* sorted_idx, void* stream) {
-    return importance_impl<false>(z, weights, R, S, Sf, u, z_fine, z_sorted, sorted_idx, nullptr, nullptr, stream);
+    return danbo_importance_samples_rays(z, weights, R, S, Sf, u, z_fine, z_sorted, sorted_idx, nullptr, nullptr, stream);
 }
 extern "C" int danbo_importance_samples_rays(const float* z, const float* weights, int R, int S, int Sf, const float* u,
                                               float* z_fine, float* z_sorted, int32_t* sorted_idx, const int32_t* ray_list,
                                               const int32_t* ray_count, void* stream) {
-    return importance_impl<false>(z, weights, R, S, Sf, u, z_fine, z_sorted, sorted_idx, ray_list, ray_count, stream);
+    return danbo_importance_samples_pdf(z, weights, R, S, Sf, u, 0, z_fine, z_sorted, sorted_idx, ray_list, ray_count, stream);
 }
 extern "C" int danbo_importance_samples_pdf(const float* z, const float* weights, int R, int S, int Sf, const float* u, int pdf,
                                              float* z_fine, float* z_sorted, int32_t* sorted_idx, const int32_t* ray_list,
                                              const int32_t* ray_count, void* stream) {
     DANBO_CHECK_ARG(pdf == 0 || pdf == 1);
-    return pdf ? importance_impl<true>(z, weights, R, S, Sf, u, z_fine, z_sorted, sorted_idx, ray_list, ray_count, stream)
-               : importance_impl<false>(z, weights, R, S, Sf, u, z_fine, z_sorted, sorted_idx, ray_list, ray_count, stream);
+    DANBO_CHECK_ARG(R > 0 && S >= 3 && Sf > 0);
+    DANBO_CHECK_ARG((ray_list == nullptr) == (ray_count == nullptr));
+    DANBO_CHECK_ARG(ray_list == nullptr || (S > 64 && S <= IMPB_MAX_S && Sf <= 64));      // (the list: the long-ray kernel only)
+    const ImportanceArgs a{z, weights, R, S, Sf, u, z_fine, z_sorted, sorted_idx, ray_list, ray_count};
+    return pdf ? importance_launch<true>(a, stream) : importance_launch<false>(a, stream);
 }
 
+struct CompositeImportanceArgs {
+    const float *raw, *raw_empty;
+    const uint32_t* valid_bits;
+    const float *z, *rays_d;
+    int R, S, Sf;
+    float B;
+    const float *noise, *u;
+    float *rgb_map, *disp, *acc, *weights, *alpha, *z_fine, *z_sorted;
+    int32_t* sorted_idx;
+    const int32_t *ray_list, *ray_count;
+};
 template <bool TWO, int DA>
-static int composite_importance_impl(const float* raw, const float* raw_empty, const uint32_t* valid_bits, const float* z,
-                                     const float* rays_d, int R, int S, int Sf, float B, const float* noise, const float* u,
-                                     float* rgb_map, float* disp, float* acc, float* weights, float* alpha, float* z_fine,
-                                     float* z_sorted, int32_t* sorted_idx, const int32_t* ray_list, const int32_t* ray_count,
-                                     float shift, void* stream) {
-    DANBO_CHECK_ARG(R > 0 && S >= 3 && S <= 64 && Sf > 0 && Sf <= 64 && B > 0.f);
-    DANBO_CHECK_ARG(raw && z && rays_d && rgb_map && disp && acc && z_fine && z_sorted && sorted_idx);
-    DANBO_CHECK_ARG((valid_bits == nullptr) || (raw_empty != nullptr));
-    DANBO_CHECK_ARG((ray_list == nullptr) == (ray_count == nullptr));
+static int composite_importance_launch(const CompositeImportanceArgs& a, float shift, void* stream) {
     static const int resident[2] = {resident_grid(k_composite_importance<false, TWO, DA>, 1L << 40, 256),
                                     resident_grid(k_composite_importance<true, TWO, DA>, 1L << 40, 256)};
-    const dim3 grid((unsigned)std::min<long>(ceil_div((long)R * 64, 256), resident[u ? 0 : 1])), block(256);
-    const float4* r4 = reinterpret_cast<const float4*>(raw);
-    const float4* e4 = reinterpret_cast<const float4*>(raw_empty);
-    if (u)
-        hipLaunchKernelGGL((k_composite_importance<false, TWO, DA>), grid, block, 0, (hipStream_t)stream, r4, e4, valid_bits, z, rays_d,
-                           R, S, Sf, B, noise, u, rgb_map, disp, acc, weights, alpha, z_fine, z_sorted, sorted_idx, ray_list, ray_count,
-                           ray_scatter(R), shift);
+    const dim3 grid((unsigned)std::min<long>(ceil_div((long)a.R * 64, 256), resident[a.u ? 0 : 1])), block(256);
+    const float4* r4 = reinterpret_cast<const float4*>(a.raw);
+    const float4* e4 = reinterpret_cast<const float4*>(a.raw_empty);
+    if (a.u)
+        hipLaunchKernelGGL((k_composite_importance<false, TWO, DA>), grid, block, 0, (hipStream_t)stream, r4, e4, a.valid_bits, a.z, a.rays_d,
+                           a.R, a.S, a.Sf, a.B, a.noise, a.u, a.rgb_map, a.disp, a.acc, a.weights, a.alpha, a.z_fine, a.z_sorted, a.sorted_idx,
+                           a.ray_list, a.ray_count, ray_scatter(a.R), shift);
     else
-        hipLaunchKernelGGL((k_composite_importance<true, TWO, DA>), grid, block, 0, (hipStream_t)stream, r4, e4, valid_bits, z, rays_d,
-                           R, S, Sf, B, noise, u, rgb_map, disp, acc, weights, alpha, z_fine, z_sorted, sorted_idx, ray_list, ray_count,
-                           ray_scatter(R), shift);
+        hipLaunchKernelGGL((k_composite_importance<true, TWO, DA>), grid, block, 0, (hipStream_t)stream, r4, e4, a.valid_bits, a.z, a.rays_d,
+                           a.R, a.S, a.Sf, a.B, a.noise, a.u, a.rgb_map, a.disp, a.acc, a.weights, a.alpha, a.z_fine, a.z_sorted, a.sorted_idx,
+                           a.ray_list, a.ray_count, ray_scatter(a.R), shift);
     DANBO_LAUNCH_RET();
 }
 extern "C" int danbo_composite_importance_fwd(const float* raw, const float* raw_empty, const uint32_t* valid_bits,
@@ -1514,8 +1529,8 @@ extern "C" int danbo_composite_importance_fwd(const float* raw, const float* raw
                                                float* acc, float* weights, float* alpha, float* z_fine, float* z_sorted,
                                                int32_t* sorted_idx, const int32_t* ray_list, const int32_t* ray_count,
                                                void* stream) {
-    return composite_importance_impl<false, DENSITY_RELU>(raw, raw_empty, valid_bits, z, rays_d, R, S, Sf, B, noise, u, rgb_map, disp, acc,
-                                                          weights, alpha, z_fine, z_sorted, sorted_idx, ray_list, ray_count, 0.f, stream);
+    return danbo_composite_importance_pdf_fwd(raw, raw_empty, valid_bits, z, rays_d, R, S, Sf, B, noise, u, 0, rgb_map, disp, acc, weights,
+                                              alpha, z_fine, z_sorted, sorted_idx, ray_list, ray_count, stream);
 }
 extern "C" int danbo_composite_importance_pdf_fwd(const float* raw, const float* raw_empty, const uint32_t* valid_bits,
                                                    const float* z, const float* rays_d, int R, int S, int Sf, float B,
@@ -1535,12 +1550,16 @@ extern "C" int danbo_composite_importance_pdf_fwd_act(const float* raw, const fl
                                                        int act, float shift, void* stream) {
     DANBO_CHECK_ARG(pdf == 0 || pdf == 1);
     DANBO_CHECK_DENSITY_ACT(act, shift);
-#define DANBO_CI(TWO_, DA_, SH_)                                                                                                   \
-    composite_importance_impl<TWO_, DA_>(raw, raw_empty, valid_bits, z, rays_d, R, S, Sf, B, noise, u, rgb_map, disp, acc, weights, \
-                                         alpha, z_fine, z_sorted, sorted_idx, ray_list, ray_count, SH_, stream)
-    if (act == DENSITY_SOFTPLUS) return pdf ? DANBO_CI(true, DENSITY_SOFTPLUS, shift) : DANBO_CI(false, DENSITY_SOFTPLUS, shift);
-    return pdf ? DANBO_CI(true, DENSITY_RELU, 0.f) : DANBO_CI(false, DENSITY_RELU, 0.f);
-#undef DANBO_CI
+    DANBO_CHECK_ARG(R > 0 && S >= 3 && S <= 64 && Sf > 0 && Sf <= 64 && B > 0.f);
+    DANBO_CHECK_ARG(raw && z && rays_d && rgb_map && disp && acc && z_fine && z_sorted && sorted_idx);
+    DANBO_CHECK_ARG((valid_bits == nullptr) || (raw_empty != nullptr));
+    DANBO_CHECK_ARG((ray_list == nullptr) == (ray_count == nullptr));
+    const CompositeImportanceArgs a{raw, raw_empty, valid_bits, z, rays_d, R, S, Sf, B, noise, u, rgb_map, disp, acc, weights, alpha,
+                                    z_fine, z_sorted, sorted_idx, ray_list, ray_count};
+    if (act == DENSITY_SOFTPLUS)
+        return pdf ? composite_importance_launch<true, DENSITY_SOFTPLUS>(a, shift, stream)
+                   : composite_importance_launch<false, DENSITY_SOFTPLUS>(a, shift, stream);
+    return pdf ? composite_importance_launch<true, DENSITY_RELU>(a, 0.f, stream) : composite_importance_launch<false, DENSITY_RELU>(a, 0.f, stream);
 }
 
 extern "C" int danbo_flat_rays(const float* t_lo, const uint32_t* ray_flat, int R, int S, int Sf, float* rgb0, float* disp0, float* acc0, float* weights0, float* alpha0, float* z_fine,
@@ -1555,20 +1574,30 @@ extern "C" int danbo_flat_rays(const float* t_lo, const uint32_t* ray_flat, int 
     DANBO_LAUNCH_RET();
 }
 
-template <int DA>
-static int composite_merged_impl(const float* raw_a, const float* raw_b, const float* raw_empty,
-                                 const uint32_t* bits_a, const uint32_t* bits_b, const int32_t* sorted_idx,
-                                 const float* z_sorted, const float* rays_d, int R, int S, int Sf, float B,
-                                 const float* noise, float* rgb_map, float* disp, float* acc, float* weights,
-                                 float* alpha, float* raw_sorted, const int32_t* ray_list, const int32_t* ray_count,
-                                 float shift, void* stream) {
+extern "C" int danbo_composite_merged_fwd(const float* raw_a, const float* raw_b, const float* raw_empty,
+                                           const uint32_t* bits_a, const uint32_t* bits_b, const int32_t* sorted_idx,
+                                           const float* z_sorted, const float* rays_d, int R, int S, int Sf, float B,
+                                           const float* noise, float* rgb_map, float* disp, float* acc, float* weights,
+                                           float* alpha, float* raw_sorted, const int32_t* ray_list, const int32_t* ray_count,
+                                           void* stream) {
+    return danbo_composite_merged_fwd_act(raw_a, raw_b, raw_empty, bits_a, bits_b, sorted_idx, z_sorted, rays_d, R, S, Sf, B, noise, rgb_map,
+                                          disp, acc, weights, alpha, raw_sorted, ray_list, ray_count, DENSITY_RELU, 0.f, stream);
+}
+extern "C" int danbo_composite_merged_fwd_act(const float* raw_a, const float* raw_b, const float* raw_empty,
+                                               const uint32_t* bits_a, const uint32_t* bits_b, const int32_t* sorted_idx,
+                                               const float* z_sorted, const float* rays_d, int R, int S, int Sf, float B,
+                                               const float* noise, float* rgb_map, float* disp, float* acc, float* weights,
+                                               float* alpha, float* raw_sorted, const int32_t* ray_list, const int32_t* ray_count,
+                                               int act, float shift, void* stream) {
+    DANBO_CHECK_DENSITY_ACT(act, shift);
     DANBO_CHECK_ARG(R > 0 && S > 0 && Sf > 0 && B > 0.f && raw_a && raw_b && sorted_idx && z_sorted && rays_d);
     DANBO_CHECK_ARG(rgb_map && disp && acc && ((bits_a == nullptr && bits_b == nullptr) || raw_empty != nullptr));
     DANBO_CHECK_ARG((ray_list == nullptr) == (ray_count == nullptr));
     const float4 *a4 = reinterpret_cast<const float4*>(raw_a), *b4 = reinterpret_cast<const float4*>(raw_b);
     const float4* e4 = reinterpret_cast<const float4*>(raw_empty);
     float4* rs4 = reinterpret_cast<float4*>(raw_sorted);
-    if constexpr (DA == DENSITY_SOFTPLUS) {
+    // two plain kernels (composite_merged_body.inc), so the two launches are written out
+    if (act == DENSITY_SOFTPLUS) {
         static const int per_launch = resident_grid(k_composite_merged_softplus, 1L << 40, 256);
         hipLaunchKernelGGL(k_composite_merged_softplus, dim3((unsigned)std::min<long>(ceil_div((long)R * 64, 256), per_launch)), dim3(256), 0,
                            (hipStream_t)stream, a4, b4, e4, bits_a, bits_b, sorted_idx, z_sorted, rays_d, R, S, Sf, B, noise, rgb_map, disp, acc,
@@ -1580,27 +1609,4 @@ static int composite_merged_impl(const float* raw_a, const float* raw_b, const f
                            weights, alpha, rs4, ray_list, ray_count, ray_scatter(R));
     }
     DANBO_LAUNCH_RET();
-}
-extern "C" int danbo_composite_merged_fwd(const float* raw_a, const float* raw_b, const float* raw_empty,
-                                           const uint32_t* bits_a, const uint32_t* bits_b, const int32_t* sorted_idx,
-                                           const float* z_sorted, const float* rays_d, int R, int S, int Sf, float B,
-                                           const float* noise, float* rgb_map, float* disp, float* acc, float* weights,
-                                           float* alpha, float* raw_sorted, const int32_t* ray_list, const int32_t* ray_count,
-                                           void* stream) {
-    return composite_merged_impl<DENSITY_RELU>(raw_a, raw_b, raw_empty, bits_a, bits_b, sorted_idx, z_sorted, rays_d, R, S, Sf, B, noise,
-                                               rgb_map, disp, acc, weights, alpha, raw_sorted, ray_list, ray_count, 0.f, stream);
-}
-extern "C" int danbo_composite_merged_fwd_act(const float* raw_a, const float* raw_b, const float* raw_empty,
-                                               const uint32_t* bits_a, const uint32_t* bits_b, const int32_t* sorted_idx,
-                                               const float* z_sorted, const float* rays_d, int R, int S, int Sf, float B,
-                                               const float* noise, float* rgb_map, float* disp, float* acc, float* weights,
-                                               float* alpha, float* raw_sorted, const int32_t* ray_list, const int32_t* ray_count,
-                                               int act, float shift, void* stream) {
-    DANBO_CHECK_DENSITY_ACT(act, shift);
-    return act == DENSITY_SOFTPLUS
-               ? composite_merged_impl<DENSITY_SOFTPLUS>(raw_a, raw_b, raw_empty, bits_a, bits_b, sorted_idx, z_sorted, rays_d, R, S, Sf, B,
-                                                         noise, rgb_map, disp, acc, weights, alpha, raw_sorted, ray_list, ray_count, shift,
-                                                         stream)
-               : composite_merged_impl<DENSITY_RELU>(raw_a, raw_b, raw_empty, bits_a, bits_b, sorted_idx, z_sorted, rays_d, R, S, Sf, B,
-                                                     noise, rgb_map, disp, acc, weights, alpha, raw_sorted, ray_list, ray_count, 0.f, stream);
 }

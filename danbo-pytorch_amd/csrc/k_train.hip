@@ -29,18 +29,6 @@ using namespace danbo;
 
 namespace {
 
-struct Carver {
-    char* base;
-    size_t used;
-    template <class T>
-    T* take(size_t n) {
-        used = (used + 255) & ~(size_t)255;
-        T* p = base ? reinterpret_cast<T*>(base + used) : nullptr;
-        used += n * sizeof(T);
-        return p;
-    }
-};
-
 constexpr int LD_VIN = 156;
 // running max |.| slots: [0, 16) belong to the fused trunk's backward (dz_0 .. dz_7, d pre_v, d alpha), then the raw gradients
 enum { MX_TRUNK = 0, MX_DPRE_V = 8, MX_DALPHA = 9, MX_RAW = 16, MX_COUNT };
@@ -86,7 +74,7 @@ TrainBuffers carve(Carver& c, const Shapes& s, const DanboTrainModel* m, long dw
     const size_t nf = (n + 127) / 128 * 128 + 128;
     b.rows_pad = (long)nf;
     // ---- zero block
-    c.used = (c.used + 255) & ~(size_t)255;
+    c.align();
     b.zero_begin = c.base ? c.base + c.used : nullptr;
     b.cnt = c.take<int32_t>(8);
     b.cntb = c.take<int32_t>(J);
@@ -272,8 +260,6 @@ __global__ __launch_bounds__(256) void k_fill_raw_lazy(const float4* __restrict_
         if (bits[i] == 0u) raw[i] = raw_empty[i / S];
 }
 
-#define DANBO_TRY(call) do { const int rc_ = (call); if (rc_ != 0) return rc_; } while (0)
-
 // Independent branches of the step run on side streams (fork: the side stream waits for an event recorded on the caller's
 // stream; join: the caller's stream waits for the side stream's event).  Inside a stream capture these cross-stream waits become
 // the edges of the HIP graph, so a replay runs the branches concurrently.  One set per device, created on first use -- which
@@ -326,12 +312,12 @@ struct ForkGuard {
 extern "C" size_t danbo_train_workspace(const DanboTrainModel* m, int R, int G, int S, int Sf, int chunk) {
     if (!model_ok(m) || R < 1 || G < 1 || S < 3 || Sf < 1 || chunk < 1) return 0;
     Shapes s{R, G, S, Sf, chunk, m->graph_width, m->n_codes, (long)R * (S + Sf + 1)};
-    Carver c{nullptr, 0};
+    Carver c;
     TrainBuffers b0 = carve(c, s, m, 0);
     DanboDwLayer L[N_DW];
     describe_dw(m, b0, L);
     const long dw = danbo_dw16_scratch_floats(L, N_DW, DW_SLICES);
-    Carver c2{nullptr, 0};
+    Carver c2;
     carve(c2, s, m, dw);
     return c2.used + 512;
 }
@@ -339,7 +325,7 @@ extern "C" size_t danbo_train_workspace(const DanboTrainModel* m, int R, int G, 
 extern "C" int danbo_train_workspace_view(const DanboTrainModel* m, int R, int G, int S, int Sf, int chunk, void* workspace, DanboTrainView* v) {
     DANBO_CHECK_ARG(model_ok(m) && workspace && v && R >= 1 && G >= 1 && S >= 3 && Sf >= 1 && chunk >= 1);
     Shapes sh{R, G, S, Sf, chunk, m->graph_width, m->n_codes, (long)R * (S + Sf + 1)};
-    Carver c{reinterpret_cast<char*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255), 0};
+    Carver c(workspace);
     const TrainBuffers b = carve(c, sh, m, 0);      // (the weight-gradient scratch lies behind everything named here)
     v->z_coarse = b.z_c; v->z_fine = b.z_f; v->z_sorted = b.z_sorted; v->order = b.order; v->bits_coarse = b.bits_c; v->bits_fine = b.bits_f;
     return 0;
@@ -365,12 +351,12 @@ static int train_step_impl(const DanboTrainModel* m, const DanboTrainBatch* bt, 
     Shapes sh{R, G, S, Sf, bt->chunk, m->graph_width, m->n_codes, (long)R * (S + Sf + 1)};
     DanboDwLayer dwl[N_DW];
     {
-        Carver c0{nullptr, 0};
+        Carver c0;
         TrainBuffers b0 = carve(c0, sh, m, 0);
         describe_dw(m, b0, dwl);
     }
     const long dw_floats = danbo_dw16_scratch_floats(dwl, N_DW, DW_SLICES);
-    Carver c{reinterpret_cast<char*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255), 0};
+    Carver c(workspace);
     const TrainBuffers b = carve(c, sh, m, dw_floats);
     describe_dw(m, b, dwl);
     DanboTrunkWeights tw;

@@ -14,7 +14,6 @@
 namespace danbo {
 
 constexpr int HW = 256, HVW = 128;
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------------------------------------------------------------
 // cview[r, f] = b_eff[f] + sum_k vin[r, k] W_v[f, 256 + k]:  128 threads = features, 8 rays per workgroup
@@ -116,11 +115,11 @@ __global__ __launch_bounds__(128) void k_train_view_grad(const float* __restrict
         int r = r_begin;
         for (; r + VG_U <= r_end && full; r += VG_U) {
             float dc[VG_U];
-            f32x4v v[VG_U][2];
+            f32x4 v[VG_U][2];
 #pragma unroll
             for (int u = 0; u < VG_U; ++u) {
                 dc[u] = d_cview[(size_t)(r + u) * HVW + f];
-                const f32x4v* vp = reinterpret_cast<const f32x4v*>(vin + (size_t)(r + u) * ldv + k0);
+                const f32x4* vp = reinterpret_cast<const f32x4*>(vin + (size_t)(r + u) * ldv + k0);
                 v[u][0] = vp[0];
                 v[u][1] = vp[1];
             }

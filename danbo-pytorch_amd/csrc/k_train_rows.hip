@@ -18,8 +18,6 @@
 
 namespace danbo {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ void atomic_max_abs(float* slot, float v) {
     if (v > 0.f) atomicMax(reinterpret_cast<unsigned*>(slot), __builtin_bit_cast(unsigned, v));
 }
@@ -64,14 +62,10 @@ __global__ __launch_bounds__(256) void k_train_view_inputs(const float* __restri
             if (ray_mode == 1) {   // root_local: skts[g, 0, :3, :3] d   (sequential-k sum like torch.matmul)
                 const float* m = skts + (size_t)(r / (R / G)) * J * 16;
                 float t[3];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) t[k] = add_rn(add_rn(mul_rn(m[4 * k], d[0]), mul_rn(m[4 * k + 1], d[1])), mul_rn(m[4 * k + 2], d[2]));
+                rotate_unfused(m, d, t);
                 d[0] = t[0]; d[1] = t[1]; d[2] = t[2];
             }
-            if (normalise) {       // F.normalize(p = 2, eps = 1e-12)
-                const float nrm = fmaxf(norm3_torch(d[0], d[1], d[2]), 1e-12f);
-                d[0] = div_rn(d[0], nrm); d[1] = div_rn(d[1], nrm); d[2] = div_rn(d[2], nrm);
-            }
+            if (normalise) normalize3(d);
             if (c < 3) out = d[c];
             else {
                 const int b = (c - 3) / 3, k = (c - 3) % 3, l = b >> 1;

@@ -11,9 +11,6 @@
 
 namespace danbo {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int M16_BM = 128;            // rows per workgroup iteration
 constexpr int CHUNK_BYTES = 32768;     // 32 fragment pieces of 1 KB
 constexpr int RING_SLOTS = 4;

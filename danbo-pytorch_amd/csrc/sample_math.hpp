@@ -69,7 +69,17 @@ DANBO_HD void sample_point(const float* o, const float* d, float z, float* p) {
     p[2] = add_rn(o[2], mul_rn(d[2], z));
 }
 
-// ((m0*x + m1*y) + m2*z) + m3 for the three rows of a row-major 4x4 (only rows 0..2 read)
+// (m0*x + m1*y) + m2*z for the three rows of a row-major 4x4: the rotation alone, what a DIRECTION takes (torch.matmul's
+// sequential-k order).  q must not alias d.
+DANBO_HD void rotate_unfused(const float* M, const float* d, float* q) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float* r = M + 4 * k;
+        q[k] = add_rn(add_rn(mul_rn(r[0], d[0]), mul_rn(r[1], d[1])), mul_rn(r[2], d[2]));
+    }
+}
+// ((m0*x + m1*y) + m2*z) + m3: rotate_unfused's sum plus the translation column (only rows 0..2 read).  Restated, not a call
+// of rotate_unfused: that form moved the assembly of the cull / gather / assignment kernels (profiles/one_definition_measured.txt)
 DANBO_HD void affine_unfused(const float* M, const float* p, float* q) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -78,6 +88,11 @@ DANBO_HD void affine_unfused(const float* M, const float* p, float* q) {
         s = add_rn(s, mul_rn(r[2], p[2]));
         q[k] = add_rn(s, r[3]);
     }
+}
+// F.normalize(d, p = 2, eps = 1e-12) of a 3-vector, in place: d / max(|d|, 1e-12)
+DANBO_HD void normalize3(float* d) {
+    const float den = fmaxf(norm3_torch(d[0], d[1], d[2]), 1e-12f);
+    d[0] = div_rn(d[0], den); d[1] = div_rn(d[1], den); d[2] = div_rn(d[2], den);
 }
 
 // world -> bone-local -> bone-aligned  (core/encoders.py:288-303,442-444)
@@ -136,6 +151,17 @@ DANBO_HD void gather_bone_features(VolPtr vol, const float* pt, const float* abs
 }
 
 DANBO_HD float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// colour of a sample (core/networks/nerf.py:281-347): sigmoid(logit) * 1.002 - 0.001, two roundings.  rgb_affine: of the sigmoid
+// itself, for the code that keeps it (the composite's backward)
+DANBO_HD float rgb_affine(float s) { return sub_rn(mul_rn(s, 1.002f), 0.001f); }
+DANBO_HD float rgb_of_logit(float x) { return rgb_affine(sigmoidf_(x)); }
+// disparity of a ray from its weighted depth and accumulated weight: 1 / max(1e-10, depth / (acc + 1e-10)), 0 where
+// torch.isclose(acc, 0): |acc| <= 1e-8 + 1e-5 * 0
+DANBO_HD float disp_of(float depth, float acc) {
+    const float dsp = div_rn(1.0f, fmaxf(1e-10f, div_rn(depth, add_rn(acc, 1e-10f))));
+    return fabsf(acc) <= 1e-8f ? 0.f : dsp;
+}
 
 // ---- density activation (get_density_fn, core/raycasters.py:192-200): relu(x) or softplus(x - shift) ----
 // A compile-time parameter of every composite (DA); the shift is a run-time float that the relu forms never read.
@@ -206,7 +232,8 @@ DANBO_HD bool bone_box_steps(const float* skt, const float* align, const float* 
                              const float* o, const float* d, float* smin, float* smax) {
     const float bound = 1.3f, eps = 1e-4f;
     float ol[3], ot[3], dl[3], dt[3];
-    // origin: full affine; direction: rotation only.  (torch.matmul order: sequential k.)
+    // origin: full affine (affine_unfused); direction: rotation only (rotate_unfused).  Restated: either call moved k_box_bounds'
+    // registers (profiles/one_definition_measured.txt)
     for (int k = 0; k < 3; ++k) {
         const float* r = skt + 4 * k;
         ol[k] = add_rn(add_rn(add_rn(mul_rn(r[0], o[0]), mul_rn(r[1], o[1])), mul_rn(r[2], o[2])), r[3]);
@@ -258,6 +285,21 @@ DANBO_HD float pdf_weight(float w0, float w1, float w2) {
     return add_rn(add_rn(mul_rn(0.5f, add_rn(fmaxf(w0, w1), fmaxf(w1, w2))), 0.01f), 1e-5f);
 }
 
+// ---- inverse CDF of one draw (sample_pdf, core/utils/ray_utils.py:159-203) ----
+// lo = searchsorted(cdf, u, right=True) over the ncdf bin edges; the edges on either side of the draw, clamped to the table
+DANBO_HD int cdf_below(int lo) { return lo - 1 > 0 ? lo - 1 : 0; }
+DANBO_HD int cdf_above(int lo, int ncdf) { return lo < ncdf - 1 ? lo : ncdf - 1; }
+// the depth of draw uk between the bin mid-points b0, b1 whose cdf values are c0, c1 (a bin narrower than 1e-5 counts as 1)
+DANBO_HD float inverse_cdf_point(float uk, float c0, float c1, float b0, float b1) {
+    float denom = sub_rn(c1, c0);
+    if (denom < 1e-5f) denom = 1.0f;
+    const float t = div_rn(sub_rn(uk, c0), denom);
+    return add_rn(b0, mul_rn(t, sub_rn(b1, b0)));
+}
+
+// rank rule of the merged order inside ONE of the two sequences: (za, ia) comes before (zb, ib) in a stable sort by depth
+DANBO_HD bool sorts_before(float za, int ia, float zb, int ib) { return (za < zb) || (za == zb && ia < ib); }
+
 // ---- importance sampling of one ray (pdf + inverse CDF + stable merge) --------------------
 // core/utils/ray_utils.py:159-203,257-291.  z, w: [S]; u: [Sf] or NULL (linspace);
 // scratch cdf: [S-1] floats... caller provides `cdf` with room for S floats.
@@ -287,15 +329,10 @@ DANBO_HD void importance_ray(const float* z, const float* w, int S, int Sf, cons
             const int mid = (lo_i + hi_i) >> 1;
             if (cdf[mid] > uk) hi_i = mid; else lo_i = mid + 1;
         }
-        const int below = lo_i - 1 > 0 ? lo_i - 1 : 0;
-        const int above = lo_i < ncdf - 1 ? lo_i : ncdf - 1;
-        const float c0 = cdf[below], c1 = cdf[above];
+        const int below = cdf_below(lo_i), above = cdf_above(lo_i, ncdf);
         const float b0 = mul_rn(0.5f, add_rn(z[below + 1], z[below]));
         const float b1 = mul_rn(0.5f, add_rn(z[above + 1], z[above]));
-        float denom = sub_rn(c1, c0);
-        if (denom < 1e-5f) denom = 1.0f;
-        const float t = div_rn(sub_rn(uk, c0), denom);
-        z_fine[k] = add_rn(b0, mul_rn(t, sub_rn(b1, b0)));
+        z_fine[k] = inverse_cdf_point(uk, cdf[below], cdf[above], b0, b1);
     }
     // stable merge, coarse first on ties (torch.sort of cat([z, z_fine]))
     int a = 0, b = 0;
@@ -322,9 +359,9 @@ DANBO_HD void composite_ray(const float* raw, const float* z, const float* d, in
         const float al = sub_rn(1.0f, expf(-mul_rn(sg, dist)));
         const float w = mul_rn(al, T);
         T = mul_rn(T, add_rn(sub_rn(1.0f, al), 1e-10f));
-        const float cr = sub_rn(mul_rn(sigmoidf_(raw[4 * s + 0]), 1.002f), 0.001f);
-        const float cg = sub_rn(mul_rn(sigmoidf_(raw[4 * s + 1]), 1.002f), 0.001f);
-        const float cb = sub_rn(mul_rn(sigmoidf_(raw[4 * s + 2]), 1.002f), 0.001f);
+        const float cr = rgb_of_logit(raw[4 * s + 0]);
+        const float cg = rgb_of_logit(raw[4 * s + 1]);
+        const float cb = rgb_of_logit(raw[4 * s + 2]);
         r = add_rn(r, mul_rn(w, cr));
         g = add_rn(g, mul_rn(w, cg));
         b = add_rn(b, mul_rn(w, cb));
@@ -334,10 +371,7 @@ DANBO_HD void composite_ray(const float* raw, const float* z, const float* d, in
         if (alpha_out) alpha_out[s] = al;
     }
     rgb_map[0] = r; rgb_map[1] = g; rgb_map[2] = b;
-    float dsp = div_rn(1.0f, fmaxf(1e-10f, div_rn(depth, add_rn(acc, 1e-10f))));
-    // torch.isclose(acc, 0): |acc| <= 1e-8 + 1e-5*0
-    if (fabsf(acc) <= 1e-8f) dsp = 0.f;
-    *disp = dsp;
+    *disp = disp_of(depth, acc);
     *acc_out = fminf(acc, 1.0f);
 }
 

@@ -134,6 +134,81 @@ def test_head_layer_with_colour_epilogue_equals_head_layer_plus_colour_kernel(S,
     assert torch.equal(got[..., 3], old[..., 3])                                   # the density logit: the same GEMM, the same bits
 
 
+def _fma32(a, b, c):
+    """(Why not float32(float64(a) * b + c): that rounds twice, to float64 and then to float32, and where the float64 sum lands exactly
+    between two float32 values the second rounding can go the other way than the one rounding of a real fma -- a last-bit difference
+    that a bitwise assertion would report as a kernel bug.)
+    fmaf(a, b, c) of float32 arrays, exactly: round32(a b + c) with ONE rounding.  a b is exact in float64 (48 bits); TwoSum gives
+    s = round64(a b + c) and its error e exactly.  float32(s) is the answer unless s sits exactly midway between two neighbouring
+    float32 values (the only place where the discarded e decides): there the sign of e picks the neighbour, e = 0 leaves the tie
+    to float32(s)'s round-to-even.  (|e| <= ulp64(s) / 2 cannot carry s + e across a midpoint that s is not on: both are float64.)"""
+    p = a.astype(np.float64) * b.astype(np.float64)
+    c = c.astype(np.float64)
+    s = p + c
+    bb = s - p
+    e = (p - (s - bb)) + (c - bb)
+    r = s.astype(np.float32)
+    r64 = r.astype(np.float64)
+    other = np.where(r64 < s, np.nextafter(r, np.float32(np.inf)), np.nextafter(r, np.float32(-np.inf))).astype(np.float64)
+    tie = (r64 != s) & (np.abs(s - r64) == np.abs(other - s))
+    lo, hi = np.minimum(r64, other), np.maximum(r64, other)
+    return np.where(tie & (e > 0), hi, np.where(tie & (e < 0), lo, r64)).astype(np.float32)
+
+
+@pytest.mark.parametrize("rays,S,VW", [(3, 5, 68), (2, 8, 256), (1, 1, 4)])
+def test_colour_head_render_and_training_forms_are_one_body(rays, S, VW):
+    """danbo_anerf_color_fwd and danbo_anerf_color_train_fwd are one device body (csrc/anerf_wave.hpp anerf_color_body): on the same
+    featv, cutoff weights, C, rgb weights and alpha, with table_ray[r] = table[code(cam_idx[r])] (one index of -1: the mean-code
+    row), raw is bit-equal, and the hv the training form keeps is bit-equal to relu of the pre-activation in the kernel's own sum
+    order restated in float32: (featv + table) then one fmaf per joint, j = 0 .. 23.  (3, 5, 68): the sample tail of the 4-unrolled
+    loop and the column tail of the 64-lane split; (2, 8, 256): the full width; (1, 1, 4): the smallest."""
+    from core import _hip, hip_ops as ops
+    gen = torch.Generator(device="cpu").manual_seed(11)
+    n, n_codes = rays * S, 3
+    rnd = lambda *sh, sc=1.0: (torch.randn(*sh, generator=gen) * sc).to(DEV)  # noqa: E731
+    featv, alpha = rnd(n, VW), rnd(n)
+    w = torch.rand(n, 24, generator=gen).to(DEV)
+    C, table = rnd(24, rays, VW, sc=0.3), rnd(n_codes + 1, VW, sc=0.3)
+    rgb_w, rgb_b = rnd(3, VW, sc=0.2), rnd(3, sc=0.1)
+    cam = torch.tensor([-1, 0, 5][:rays], dtype=torch.int64, device=DEV)                # -1: the mean row; 5: clamped to n_codes - 1
+    code = torch.where(cam < 0, torch.full_like(cam, n_codes), cam.clamp(max=n_codes - 1))
+    table_ray = table[code].contiguous()
+    raw = torch.full((rays, S, 4), 7.0, device=DEV)
+    ops.anerf_color(featv, w, C, table, cam, 0, rays, S, rgb_w, rgb_b, alpha, raw)
+    raw_t = torch.full((rays, S, 4), 7.0, device=DEV)
+    hv = torch.full((n, VW), 7.0, device=DEV)
+    p = lambda t: t.data_ptr()  # noqa: E731
+    _hip.call("danbo_anerf_color_train_fwd", p(featv), VW, p(w), p(C), p(table_ray), rays, rays, S, VW, p(rgb_w), p(rgb_b), p(alpha), 1,
+              p(hv), p(raw_t), ops._stream())
+    assert torch.equal(raw, raw_t)
+    ray = np.arange(n) // S
+    x = N(featv) + N(table_ray)[ray]
+    for j in range(24):
+        x = _fma32(N(w)[:, j:j + 1], N(C)[j][ray], x)
+    assert np.array_equal(N(hv).view(np.uint32), np.maximum(x, np.float32(0)).view(np.uint32))
+
+
+@pytest.mark.parametrize("Lv", [0, 2, 4])
+def test_view_encoding_kernel_and_view_constants_share_one_encoding(Lv):
+    """danbo_anerf_view_pe_fwd and danbo_anerf_view_consts_fwd form the encoding with one function (csrc/anerf_wave.hpp av_ray_pe, two
+    output strides): with a one-hot wj (column k of joint j selects entry k; VW = nk rounded up to 4) C[j, r, k] is bit-equal to
+    E[r, 72 b + 3 j + a], k = 3 b + a.  L_view = 2: the constants' weights in LDS; 4: the 27-register form; 0: the direction alone."""
+    from core import hip_ops as ops
+    gen = torch.Generator(device="cpu").manual_seed(13)
+    R, G, nb = 6, 2, 1 + 2 * Lv
+    nk = 3 * nb
+    VW = (nk + 3) // 4 * 4
+    rays_d = torch.randn(R, 3, generator=gen).to(DEV)
+    skts = torch.randn(G, 24, 4, 4, generator=gen).to(DEV)
+    wj = torch.zeros(24, nk, VW, device=DEV)
+    wj[:, torch.arange(nk), torch.arange(nk)] = 1.0
+    C = ops.anerf_view_consts(rays_d, skts, Lv, wj)                                     # [24, R, VW]
+    E = ops.anerf_view_pe(rays_d, skts, Lv)                                             # [R, nb * 72]: 72 b + 3 j + a
+    want = E.reshape(R, nb, 24, 3).permute(2, 0, 1, 3).reshape(24, R, nk)
+    assert torch.equal(C[:, :, :nk].view(torch.int32), want.contiguous().view(torch.int32))
+    assert bool((C[:, :, nk:] == 0).all())
+
+
 def test_small_matmul_reads_strided_operands_and_accumulates_in_float64():
     from core import hip_ops as ops
     gen = torch.Generator(device="cpu").manual_seed(9)

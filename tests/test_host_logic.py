@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import danbo_oracle as o
+import isa
 from helpers import ROOT, golden, oracle_for, max_err
 
 F = ctypes.POINTER(ctypes.c_float)
@@ -299,21 +300,13 @@ def test_kp_to_valid_rays_matches_reference():
     assert 0 < tl[0] < br[0] < int(g["W"]) - 1 and 0 < tl[1] < br[1] < int(g["H"]) - 1   # an interior box, not the frame
 
 
-def test_linear16_isa_keeps_its_hands_off_the_in_flight_row_registers(tmp_path):
+def test_linear16_isa_keeps_its_hands_off_the_in_flight_row_registers():
     """k_linear16 requests its input rows two k-steps ahead into fixed physical registers v[208:223] and keeps the weight fragments
     of two groups in v[224:255] (mlp16_core.hpp group_mfma), all of which only its inline asm names: the kernel is compiled with
     amdgpu_num_vgpr(208).  Nothing the compiler generates may touch them (a copy or spill of a register whose load is in flight
     reads stale data), every MFMA sits inside the asm, and the compiler must not add vmcnt waits of its own inside the k-step loop
     (they would drain the weight ring).  Checked on the gfx950 ISA of every instantiation."""
-    import shutil
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    src = os.path.join(ROOT, "danbo-pytorch_amd", "csrc", "k_linear16.hip")
-    out = str(tmp_path / "k_linear16.s")
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S", "--cuda-device-only", "-o", out, src],
-                   check=True, capture_output=True)
-    text = open(out).read()
+    text = isa.device_asm("k_linear16")
     pinned = r"(20[89]|21\d|22\d|23\d|24\d|25[0-5])"
     high = re.compile(r"\bv" + pinned + r"\b|v\[" + pinned + ":")
     # every instantiation <NH, NP, TRACE, FRAG>; FRAG = activations in fragment order (danbo_linear16_fwd_frag)
@@ -322,13 +315,11 @@ def test_linear16_isa_keeps_its_hands_off_the_in_flight_row_registers(tmp_path):
     for name, nh, np_, trace, frag in names:
         nh, np_, trace, frag = int(nh), int(np_), int(trace), int(frag)
         seen.add((nh, np_, trace, frag))
-        body = text[text.index(name + ":"):]
-        body = body[:body.index(".Lfunc_end")].split("\n")
+        body = isa.kernel_body(text, re.escape(name))
         assert not any("scratch_" in l for l in body), ("register spills", name)
         # outside the inline asm nothing names v208 .. v255 and there is no MFMA
-        in_asm, foreign, mfma = False, [], 0
-        for l in body:
-            in_asm = True if "ASMSTART" in l else (False if "ASMEND" in l else in_asm)
+        foreign, mfma = [], 0
+        for in_asm, l in isa.asm_lines(body):
             if not in_asm and (high.search(l) or "v_mfma" in l):
                 foreign.append(l.strip())
             mfma += "v_mfma_f32_16x16x32_f16" in l
@@ -397,30 +388,20 @@ def test_no_packed_fp32_instruction_takes_its_low_half_from_src1s_high_dword(tmp
     assert vulnerable == 0, where[:8]
 
 
-def test_dw16_isa_leaves_the_producers_load_registers_alone(tmp_path):
+def test_dw16_isa_leaves_the_producers_load_registers_alone():
     """k_dw16's producer wavefronts request their operands two steps ahead with inline-asm loads into the fixed accumulation
     registers a0 .. a95 and wait for them by count (csrc/k_dw16_regs.inc): nothing the compiler generates for the producer code may
     name those registers (a value parked there would be overwritten by a load in flight), the kernel must not spill, must fit two
     wavefronts per SIMD (256 registers), and its waits must be the counted ones."""
-    import shutil
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    src = os.path.join(ROOT, "danbo-pytorch_amd", "csrc", "k_dw16.hip")
-    out = str(tmp_path / "k_dw16.s")
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S", "--cuda-device-only", "-o", out, src],
-                   check=True, capture_output=True)
-    text = open(out).read()
-    meta = re.search(r"\.name:\s+_ZN5danbo6k_dw16ENS_6DwArgsE\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)", text)
+    text = isa.device_asm("k_dw16")
+    meta = isa.kernel_meta(text, "_ZN5danbo6k_dw16ENS_6DwArgsE", "vgpr_count")
     assert meta is not None and int(meta.group(1)) <= 256, meta and meta.group(1)
-    body = text[text.index("_ZN5danbo6k_dw16ENS_6DwArgsE:"):]
-    body = body[:body.index(".Lfunc_end")].split("\n")
+    body = isa.kernel_body(text, "_ZN5danbo6k_dw16ENS_6DwArgsE")
     assert not any("scratch_" in l for l in body)
     pinned = re.compile(r"\ba(\d+)\b|\ba\[(\d+):(\d+)\]")
     first_load = next(i for i, l in enumerate(body) if "global_load_dwordx4 a[" in l)
-    in_asm, loads, foreign = False, 0, []
-    for i, l in enumerate(body):
-        in_asm = True if "ASMSTART" in l else (False if "ASMEND" in l else in_asm)
+    loads, foreign = 0, []
+    for i, (in_asm, l) in enumerate(isa.asm_lines(body)):
         code = l.split(";")[0]
         if in_asm:
             loads += "global_load_dwordx4 a[" in code
@@ -437,36 +418,23 @@ def test_dw16_isa_leaves_the_producers_load_registers_alone(tmp_path):
     assert "vmcnt(12)" in waits, waits
 
 
-def test_ring_kernels_do_not_spill(tmp_path):
+def test_ring_kernels_do_not_spill():
     """The kernels that stream weights through an LDS ring with hand-counted vmcnt waits must not spill: a scratch access is a
     VMEM operation the compiler waits for with vmcnt(0), which drains the ring (k_pe_mlp16 with 196 B of spills moved 10x the HBM
     traffic).  Checked on the gfx950 ISA."""
-    import shutil
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    for src, kernels in (("k_mlp16.hip", ["k_pe_mlp16"]), ("k_assign16.hip", ["k_assign16ILb0E", "k_assign16ILb1E"])):
-        out = str(tmp_path / (src + ".s"))
-        subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S", "--cuda-device-only", "-o", out,
-                        os.path.join(ROOT, "danbo-pytorch_amd", "csrc", src)], check=True, capture_output=True)
-        text = open(out).read()
+    for tu, kernels in (("k_mlp16", ["k_pe_mlp16"]), ("k_assign16", ["k_assign16ILb0E", "k_assign16ILb1E"])):
+        text = isa.device_asm(tu)
         for k in kernels:
-            meta = re.search(r"\.name:\s+\S*" + k + r"\S*\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)", text)
+            meta = isa.kernel_meta(text, r"\S*" + k + r"\S*", "private_segment_fixed_size")
             assert meta is not None, k
             assert int(meta.group(1)) == 0, (k, meta.group(1))
-            body = text[text.index(re.search(r"^(_ZN5danbo\S*" + k + r"\S*):", text, re.M).group(1) + ":"):]
-            body = body[:body.index(".Lfunc_end")]
+            body = "\n".join(isa.kernel_body(text, r"_ZN5danbo\S*" + k + r"\S*"))
             assert "scratch_" not in body and "buffer_store" not in body, k
     # The training trunk's kernels run the same ring with stores in between.  They may spill a few tile-level values (pointers of
     # the row outputs) -- but no scratch access between the first and the last MFMA of the forward's layer loop, and in the
     # backward only in the once-per-tile staging branch.
-    for src, k, max_in_loop in (("k_mlp16.hip", "k_train_mlp_fwd", 0), ("k_mlp16_bwd.hip", "k_train_mlp_bwd", 0)):
-        out = str(tmp_path / (src + ".t.s"))
-        subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S", "--cuda-device-only", "-o", out,
-                        os.path.join(ROOT, "danbo-pytorch_amd", "csrc", src)], check=True, capture_output=True)
-        text = open(out).read()
-        body = text[text.index(re.search(r"^(_ZN5danbo\S*" + k + r"\S*):", text, re.M).group(1) + ":"):]
-        body = body[:body.index(".Lfunc_end")].split("\n")
+    for tu, k, max_in_loop in (("k_mlp16", "k_train_mlp_fwd", 0), ("k_mlp16_bwd", "k_train_mlp_bwd", 0)):
+        body = isa.kernel_body(isa.device_asm(tu), r"_ZN5danbo\S*" + k + r"\S*")
         mf = [i for i, l in enumerate(body) if "v_mfma" in l]
         inside = [l for i, l in enumerate(body) if "scratch_" in l and mf[0] < i < mf[-1]]
         assert len(inside) <= max_in_loop, (k, inside)
@@ -474,20 +442,15 @@ def test_ring_kernels_do_not_spill(tmp_path):
     # compiler-generated code (mlp16_core.hpp; the kernels are compiled with amdgpu_num_vgpr(224)); the training backward too.  No instruction outside the
     # inline asm may name one of them, the kernels use no scratch at all, and every MFMA of theirs is inside the asm.
     high = re.compile(r"\bv(22[4-9]|2[34]\d|25[0-5])\b|v\[(\d+):(\d+)\]")
-    for k, n_mfma, asm_file in (("k_pe_mlp16", 960, "k_mlp16.hip.s"), ("k_train_mlp_fwd", 960, "k_mlp16.hip.s"),
-                                ("k_train_mlp_bwd", 912, "k_mlp16_bwd.hip.t.s")):      # 20 chunk sites x 48; 4 + 8 x 48 + 8 x 42
-        text = open(str(tmp_path / asm_file)).read()
-        meta = re.search(r"\.name:\s+\S*" + k + r"\S*\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)", text)
+    for k, n_mfma, tu in (("k_pe_mlp16", 960, "k_mlp16"), ("k_train_mlp_fwd", 960, "k_mlp16"),
+                          ("k_train_mlp_bwd", 912, "k_mlp16_bwd")):      # 20 chunk sites x 48; 4 + 8 x 48 + 8 x 42
+        text = isa.device_asm(tu)
+        meta = isa.kernel_meta(text, r"\S*" + k + r"\S*", "private_segment_fixed_size")
         assert int(meta.group(1)) == 0, (k, meta.group(1))
-        body = text[text.index(re.search(r"^(_ZN5danbo\S*" + k + r"\S*):", text, re.M).group(1) + ":"):]
-        body = body[:body.index(".Lfunc_end")].split("\n")
-        in_asm, foreign, mfma_outside, mfma_inside = False, [], 0, 0
-        for l in body:
-            if "#ASMSTART" in l:
-                in_asm = True
-            elif "#ASMEND" in l:
-                in_asm = False
-            elif in_asm:
+        body = isa.kernel_body(text, r"_ZN5danbo\S*" + k + r"\S*")
+        foreign, mfma_outside, mfma_inside = [], 0, 0
+        for in_asm, l in isa.asm_lines(body):
+            if in_asm:
                 mfma_inside += "v_mfma" in l
             else:
                 code = l.split(";")[0]
@@ -499,7 +462,7 @@ def test_ring_kernels_do_not_spill(tmp_path):
         assert mfma_outside == 0 and mfma_inside == n_mfma, (k, mfma_outside, mfma_inside)
 
 
-def test_k3_32x32_form_register_discipline(tmp_path):
+def test_k3_32x32_form_register_discipline():
     """k_pe_mlp32 (K3 in the 32x32x16 form) names its own registers in inline assembly: the two AccVGPR result banks, the fragment
     double buffers, the epilogue temporaries (v184 .. v255).  The compiler only honours them ACROSS one asm statement; what keeps
     them safe between statements is that it has no reason to take them.  Checked on the gfx950 ISA: between the first and the last
@@ -507,32 +470,20 @@ def test_k3_32x32_form_register_discipline(tmp_path):
     behind the last MFMA -- why the view layer's accumulators are asm operands, not pinned), none touches M0 (every LDS-DMA load
     is an asm statement with its own M0 write: with builtin loads the compiler hoisted its M0 initialisation across the groups and
     the staging loads went into the ring), there is no scratch, and every MFMA sits inside the asm."""
-    import shutil
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    out = str(tmp_path / "k_mlp32.s")
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S", "--cuda-device-only", "-o", out,
-                    os.path.join(ROOT, "danbo-pytorch_amd", "csrc", "k_mlp32.hip")], check=True, capture_output=True)
-    text = open(out).read()
+    text = isa.device_asm("k_mlp32")
     k = "k_pe_mlp32"
-    meta = re.search(r"\.name:\s+\S*" + k + r"\S*\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)", text)
+    meta = isa.kernel_meta(text, r"\S*" + k + r"\S*", "private_segment_fixed_size")
     assert meta is not None and int(meta.group(1)) == 0, meta and meta.group(1)
-    body = text[text.index(re.search(r"^(_ZN5danbo\S*" + k + r"\S*):", text, re.M).group(1) + ":"):]
-    body = body[:body.index(".Lfunc_end")].split("\n")
+    body = isa.kernel_body(text, r"_ZN5danbo\S*" + k + r"\S*")
     assert not any("scratch_" in l for l in body)
     mf = [i for i, l in enumerate(body) if "v_mfma" in l]
     # 2 x 13 k-substeps of the encoding x 24 | three dense-layer sites of 16 x 24 (+ the skip layer's second form of k-substep 0) | view 16 x 12
     assert len(mf) == 2 * 13 * 24 + 3 * 16 * 24 + 24 + 16 * 12, len(mf)
     vreg = re.compile(r"\bv(\d+)\b|\bv\[(\d+):(\d+)\]")
     areg = re.compile(r"\ba(\d+)\b|\ba\[(\d+):(\d+)\]")
-    in_asm, foreign, mfma_outside, m0_outside = False, [], 0, []
-    for i, l in enumerate(body):
-        if "#ASMSTART" in l:
-            in_asm = True
-        elif "#ASMEND" in l:
-            in_asm = False
-        elif not in_asm:
+    foreign, mfma_outside, m0_outside = [], 0, []
+    for i, (in_asm, l) in enumerate(isa.asm_lines(body)):
+        if not in_asm:
             code = l.split(";")[0]
             mfma_outside += "v_mfma" in code
             if re.search(r"\bm0\b", code):
