@@ -10,7 +10,9 @@ Every pointer, whatever it points to, is a `c_void_p` (`char*`: `c_char_p`): a p
 is skipped.  A new entry point needs its declaration in the header and its implementation, and is then callable as
 `call("danbo_x", ...)`; a wrapper in hip_ops is optional.
 
-The header is $DANBO_HIP_HEADER, else danbo_hip.h beside the library, else include/danbo_hip.h of the source tree.  `lib()` refuses
+The header is $DANBO_HIP_HEADER, else danbo_hip.h beside the library, else include/danbo_hip.h of the source tree.  The
+rasteriser's two entries stand in danbo_raster.h beside it and are bound the same way into RASTER_SIGNATURES / RASTER_RESTYPES /
+RASTER_C (tables of their own: SIGNATURES and C are the statement of danbo_hip.h alone).  `lib()` refuses
 a library whose danbo_abi_version() is not the header's DANBO_ABI_VERSION (a stale build).
 
 The library is the only compute backend of this package: there is NO PyTorch/CPU fallback.  `lib()` raises if the shared object is
@@ -207,6 +209,19 @@ STRUCTS = {name: type(name, (ctypes.Structure,), {"_fields_": fields, "__doc__":
 globals().update(STRUCTS)              # _hip.DanboModel, _hip.DanboDwLayer, ...
 C = SimpleNamespace(**_constants)
 MAX_ROW_SPANS = C.DANBO_MAX_ROW_SPANS
+
+# ---- the rasteriser's entries (include/danbo_raster.h, beside danbo_hip.h): the same parser, tables of their own -- SIGNATURES and
+# C stay the statement of danbo_hip.h alone
+RASTER_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "danbo_raster.h")
+if not os.path.exists(RASTER_HEADER_PATH):
+    raise RuntimeError(f"{RASTER_HEADER_PATH} not found (the binding of the rasteriser is derived from it, it lies beside danbo_hip.h)")
+with open(RASTER_HEADER_PATH) as _f:
+    _r_functions, _r_structs, _r_constants = parse_header(_f.read())
+if _r_structs or set(_r_functions) & set(_functions) or set(_r_constants) & set(_constants):
+    raise HeaderError(f"{RASTER_HEADER_PATH} declares a struct, or a name danbo_hip.h declares")
+RASTER_SIGNATURES = {name: argtypes for name, (_, argtypes) in _r_functions.items()}
+RASTER_RESTYPES = {name: restype for name, (restype, _) in _r_functions.items()}
+RASTER_C = SimpleNamespace(**_r_constants)
 ANERF_MAX_D = C.DANBO_ANERF_MAX_D
 
 # ---- training step: the state_dict key of every slot of DanboTrainModel.p / .g (enum DanboTrainTensor; the names are Python's)
@@ -237,10 +252,10 @@ def lib():
                 f"{LIB_PATH} not found: build it with `make -C danbo-pytorch_amd/csrc` "
                 "(or __graft_entry__.build()).  There is no CPU / PyTorch fallback.")
         l = ctypes.CDLL(LIB_PATH)
-        for name, argtypes in SIGNATURES.items():
+        for name, argtypes in {**SIGNATURES, **RASTER_SIGNATURES}.items():
             fn = getattr(l, name)
             fn.argtypes = argtypes
-            fn.restype = RESTYPES[name]
+            fn.restype = RESTYPES.get(name) or RASTER_RESTYPES[name]
         if l.danbo_abi_version() != C.DANBO_ABI_VERSION:
             raise RuntimeError(f"{LIB_PATH} has ABI version {l.danbo_abi_version()}, {HEADER_PATH} declares {C.DANBO_ABI_VERSION}: "
                                "the library is stale, rebuild it with `make -C danbo-pytorch_amd/csrc`")

@@ -25,6 +25,7 @@ from core.load_data import PoseImageDataset, generate_bullet_time, get_dataset  
 from core.raycasters import create_raycaster  # noqa: E402
 from core.utils.evaluation_helpers import evaluate_in_boxes  # noqa: E402
 from core.utils.mesh_io import write_ply  # noqa: E402
+from core.utils.mesh_render import render_turntable  # noqa: E402
 from core.utils.skeleton_utils import get_smpl_l2ws  # noqa: E402
 from run_nerf import render_path  # noqa: E402
 
@@ -44,6 +45,9 @@ def config_parser():
     p.add_argument('--mesh_threshold', type=float, default=10.0, help='density of the extracted isosurface')
     p.add_argument('--mesh_normals', action='store_true', help='with --render_mesh: per-vertex normals in the .ply')
     p.add_argument('--mesh_colors', action='store_true', help='with --render_mesh: per-vertex colours (seen head-on) in the .ply')
+    p.add_argument('--mesh_render', nargs='?', const='normal', default=None, choices=['normal', 'color', 'flat'],
+                   help='with --render_mesh: the turntable of every mesh (render_mesh.py) straight from the device tensors')
+    p.add_argument('--mesh_render_res', nargs=2, type=int, default=[512, 512], help='(H, W) of the turntable frames')
     p.add_argument('--render_confd', action='store_true')
     p.add_argument('--render_entropy', action='store_true')
     p.add_argument('--selected_idxs', nargs='+', type=int, default=None)
@@ -257,23 +261,34 @@ def evaluate_metric(rgbs, accs, bboxes, gt_dict, basedir):
 
 
 @torch.no_grad()
-def render_mesh(basedir, render_kwargs, tensor_data, chunk=4096, radius=1.80, res=255, threshold=10., normals=False, colors=False):
+def render_mesh(basedir, render_kwargs, tensor_data, chunk=4096, radius=1.80, res=255, threshold=10., normals=False, colors=False,
+                turntable=None, turntable_res=(512, 512)):
     """Density on a (res+1)^3 grid around every pose and its isosurface at `threshold` (reference :1266-1281: PyMCubes and trimesh
     there, the library's own extraction kernels and core/utils/mesh_io.py here): `meshes/NNN.ply`, vertices in [-0.5, 0.5]^3, and
     the clamped grid as `meshes/NNN_sigma.npy`.  normals / colors (--mesh_normals / --mesh_colors) add per-vertex unit normals --
     the gradient of the grid, where the reference's separate render_mesh.py sums face normals (compute_normal) -- and per-vertex
-    colours of the network seen along -normal (with the frame's frame code, where the network has them) to the vertex records."""
+    colours of the network seen along -normal (with the frame's frame code, where the network has them) to the vertex records.
+    turntable ('normal' | 'color' | 'flat', --mesh_render): the 91 frames of the reference's render_mesh.py of every mesh, drawn
+    from the device tensors (core/utils/mesh_render.py) into `mesh_render/NNN.npy`, uint8 [91,H,W,3]; it computes the normals or
+    colours it needs whether or not the .ply is asked to hold them."""
     caster = render_kwargs['ray_caster']
     os.makedirs(os.path.join(basedir, 'meshes'), exist_ok=True)
+    want_n, want_c = normals or turntable == 'normal', colors or turntable == 'color'
+    if turntable:
+        os.makedirs(os.path.join(basedir, 'mesh_render'), exist_ok=True)
     kps, skts, bones, cams = tensor_data['kp'], tensor_data['skts'], tensor_data['bones'], tensor_data.get('cams')
     for i in range(len(kps)):
         cam = None if cams is None else cams[i % cams.shape[0]:i % cams.shape[0] + 1]
         verts, faces, *attrs, raw = caster(kps=kps[i:i + 1], skts=skts[i:i + 1], bones=bones[i:i + 1], radius=radius,
                                            render_kwargs=render_kwargs['preproc_kwargs'], res=res, netchunk=chunk, threshold=threshold,
-                                           return_density=True, normals=normals, colors=colors, cams=cam, fwd_type='mesh_surface')
+                                           return_density=True, normals=want_n, colors=want_c, cams=cam, fwd_type='mesh_surface')
         np.save(os.path.join(basedir, 'meshes', f'{i:03d}_sigma.npy'), np.maximum(raw.cpu().numpy(), 0))
         write_ply(os.path.join(basedir, 'meshes', f'{i:03d}.ply'), verts, faces, normals=attrs[0] if normals else None,
                   colors=attrs[-1] if colors else None)
+        if turntable and len(verts) and len(faces):
+            frames = render_turntable(verts, faces, normals=attrs[0] if want_n else None, colors=attrs[-1] if want_c else None,
+                                      size=turntable_res, shade=turntable)
+            np.save(os.path.join(basedir, 'mesh_render', f'{i:03d}.npy'), frames.cpu().numpy())
 
 
 def run_render(argv=None):
@@ -290,7 +305,8 @@ def run_render(argv=None):
     os.makedirs(basedir, exist_ok=True)
     if args.render_mesh:
         render_mesh(basedir, render_kwargs, tensor_data, res=args.mesh_res, radius=args.mesh_radius, threshold=args.mesh_threshold,
-                    normals=args.mesh_normals, colors=args.mesh_colors)
+                    normals=args.mesh_normals, colors=args.mesh_colors, turntable=args.mesh_render,
+                    turntable_res=tuple(args.mesh_render_res))
         return None
     render_kwargs = dict(render_kwargs, render_confd=args.render_confd, render_entropy=args.render_entropy)
     rgbs, _, accs, _, bboxes = render_path(render_kwargs=render_kwargs, chunk=nerf_args.chunk, ext_scale=nerf_args.ext_scale,
