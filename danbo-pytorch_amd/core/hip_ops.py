@@ -510,6 +510,70 @@ def merge_samples(a, b, idx):
     return out
 
 
+# -------------------------------------------------------------------------------------- bone-assignment maps
+PART_MODES = {"confd": 0, "entropy": 1}
+_PALETTES = {}
+
+
+def part_palette(device):
+    """the [24,3] table danbo_part_colors_fwd reads in 'confd' mode: core.networks.misc.joint_colours() -- the one definition of
+    the joint colours -- on `device`, made once per device (the first call copies from the host: not inside a graph capture)"""
+    device = torch.device(device)
+    t = _PALETTES.get(device)
+    if t is None:
+        from .networks.misc import joint_colours
+        t = joint_colours(device).contiguous()
+        if device.type != "cuda" or not torch.cuda.is_current_stream_capturing():
+            _PALETTES[device] = t
+    return t
+
+
+def part_colors(confd, mode, rgb, lst=None, cnt=None, n=None, bits=None, valid_only=False):
+    """danbo_part_colors_fwd: the colour of every listed sample from its assignment logits.  confd [rows,24]: row i belongs to
+    sample m = lst[i] (lst None: i), rows at or beyond cnt (device count; None: n) are not touched; mode 'confd' / 'entropy'; rgb
+    [..., 3] float32 over the samples (m indexes its rows) is written in place and returned.  valid_only: only the bones whose bit of
+    bits[m] is set take part (bits: bone_cull's in-volume words, by sample)."""
+    if mode not in PART_MODES:
+        raise ValueError(f"part_colors: mode must be one of {sorted(PART_MODES)}, not {mode!r}")
+    for t, name in ((confd, "confd"), (rgb, "rgb"), (lst, "list"), (cnt, "count"), (bits, "valid_bits")):
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"{name}: expected a CUDA/HIP tensor -- libdanbo_hip has no CPU fallback")
+    if confd.dtype != torch.float32 or confd.dim() != 2 or confd.shape[1] != J or not confd.is_contiguous():
+        raise ValueError("part_colors: confd must be a contiguous [rows, 24] float32 tensor")
+    if rgb.dtype != torch.float32 or not rgb.is_contiguous() or rgb.shape[-1] != 3:
+        raise ValueError("part_colors: rgb must be a contiguous [..., 3] float32 tensor")
+    if valid_only and bits is None:
+        raise ValueError("part_colors: valid_only needs the in-volume words")
+    n = confd.shape[0] if n is None else int(n)
+    if n > confd.shape[0] or (lst is None and n > rgb.numel() // 3) or (lst is not None and n > lst.numel()):
+        raise ValueError("part_colors: more rows than confd / list / rgb hold")
+    pal = part_palette(confd.device) if mode == "confd" else None
+    _call("danbo_part_colors_fwd", _p(confd), _p(bits), _p(lst), _p(cnt), n, PART_MODES[mode], 1 if valid_only else 0, _p(pal),
+          _p(rgb), _stream())
+    return rgb
+
+
+def composite_colors(rgb_a, weights, rgb_b=None, idx=None, bits_a=None, bits_b=None, flat=None, out=None):
+    """danbo_composite_colors_fwd: rgb_map [R,3] = sum over the sorted order of weights [R,S+Sf] times the samples' colours, read
+    from rgb_a [R,S,3] / rgb_b [R,Sf,3] through idx (None, with rgb_b None: the identity).  bits_*: in-volume words of samples
+    whose colour rows exist only where the word is not 0.  flat: flat_rays()'s result -- only its listed rays are written; out:
+    the [R,3] buffer to write (the frame's rgb_map / rgb0; None: a fresh one)."""
+    for t, name in ((rgb_a, "rgb_a"), (weights, "weights"), (rgb_b, "rgb_b"), (idx, "sorted_idx"), (out, "out")):
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"{name}: expected a CUDA/HIP tensor -- libdanbo_hip has no CPU fallback")
+    rgb_a, rgb_b, weights = _f32(rgb_a, "rgb_a"), _f32(rgb_b, "rgb_b"), _f32(weights, "weights")
+    R, S = rgb_a.shape[:2]
+    Sf = 0 if rgb_b is None else rgb_b.shape[1]
+    if tuple(weights.shape) != (R, S + Sf) or (idx is None) != (rgb_b is None) or (idx is not None and tuple(idx.shape) != (R, S + Sf)):
+        raise ValueError("composite_colors: weights / sorted_idx must be [R, S + Sf]; sorted_idx and rgb_b come together")
+    if out is None:
+        out = torch.empty(R, 3, device=rgb_a.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (R, 3) and out.is_contiguous()
+    _call("danbo_composite_colors_fwd", _p(rgb_a), _p(rgb_b), _p(bits_a), _p(bits_b), _p(idx), _p(weights), R, S, Sf,
+          *_ray_list(flat), _p(out), _stream())
+    return out
+
+
 # -------------------------------------------------------------------------------------- A-NeRF
 def _anerf_grid(rays_o, rays_d, skts, z, pts, nrows, width, out):
     """the shared front of the two A-NeRF encoders: the R x S sample grid as points (pts [R,S,3]) or as rays + depths (z [R,S]),

@@ -253,6 +253,20 @@ class RayCaster(nn.Module):
             return eng.render(*args, **kwargs)
         return eng.render_two_net(fine, *args, **kwargs)
 
+    _part_notice_done = False
+
+    def _part_kwargs(self, eng, render_confd, render_entropy, part_valid_only):
+        """render_confd / render_entropy (confd wins, the reference's if / elif in raw2outputs, nerf.py:306-311) as the engine's
+        part_map arguments.  A-NeRF has no assignment net: there the flags keep doing nothing, with one notice."""
+        if not (render_confd or render_entropy):
+            return {}
+        if not isinstance(eng, DanboEngine):
+            if not RayCaster._part_notice_done:
+                RayCaster._part_notice_done = True
+                print('render_confd / render_entropy: this network has no bone-assignment net -- rendering the colour image')
+            return {}
+        return dict(part_map='confd' if render_confd else 'entropy', part_valid_only=bool(part_valid_only))
+
     @staticmethod
     def _per_pose(x, G):
         return x if x.shape[0] == G else x[::max(x.shape[0] // G, 1)].contiguous()
@@ -260,17 +274,17 @@ class RayCaster(nn.Module):
     def render_rays(self, ray_batch, N_samples, kp_batch, skts=None, cyls=None, bones=None, cams=None,
                     subject_idxs=None, retraw=False, lindisp=False, perturb=0., N_importance=0, network_fine=None,
                     raw_noise_std=0., ray_noise_std=0., verbose=False, ext_scale=0.001, pytest=False, N_uniques=1,
-                    render_confd=False, render_entropy=False, preproc_kwargs={}, netchunk=1024 * 64,
+                    render_confd=False, render_entropy=False, part_valid_only=False, preproc_kwargs={}, netchunk=1024 * 64,
                     nerf_type="nerf", **kwargs):
         if N_importance <= 0:
             raise NotImplementedError("N_importance=0 raises in the reference too (raycasters.py:377)")
         if perturb or raw_noise_std or ray_noise_std or lindisp:
             raise NotImplementedError("stochastic sampling belongs to the training path")
-        # render_confd / render_entropy: accepted and -- exactly as in the reference -- without effect here: its render_rays takes
-        # the two flags (raycasters.py:265-266) but never hands them to raw2outputs (:334-337, :373-375), whose colourings
-        # (nerf.py:306-311) would moreover need raw[..., 4:], which no shipped network produces.  The colourings themselves are
-        # available on NeRF.raw2outputs (core/networks/nerf.py) for a caller that passes the assignment logits in raw[..., 4:].
+        # render_confd / render_entropy: the reference's render_rays takes the two flags (raycasters.py:265-266) but never hands
+        # them to raw2outputs (:334-337, :373-375).  Here they reach the engine, which renders what raw2outputs (nerf.py:306-313)
+        # would have made of them: rgb_map / rgb0 become the bone-assignment map (DanboEngine.render(part_map=...)).
         eng, fine = self._engines(preproc_kwargs)
+        part = self._part_kwargs(eng, render_confd, render_entropy, part_valid_only)
         G = int(N_uniques)
         skts_g, bones_g, cyls_g = self._per_pose(skts, G), self._per_pose(bones, G), self._per_pose(cyls, G)
         R = ray_batch.shape[0]
@@ -281,13 +295,13 @@ class RayCaster(nn.Module):
             if eng.cfg['use_volume_near_far']:
                 ops.near_far_boxes(rays_o, rays_d, skts_g, eng.align, eng.axis_scale, near, far)
             return self._render(eng, fine, rays_o, rays_d, skts_g, bones_g, cyls_g, cams, N_samples, N_importance,
-                                near_far=(near, far))
+                                near_far=(near, far), **part)
 
         # Small ray chunks (the reference casts `chunk // 8` = 512 rays at a time during validation) are launch-bound: the
         # ~25 kernels of the chain are captured once per chunk shape as a HIP graph and replayed.
         if self.use_graphs and R <= self.graph_max_rays and isinstance(eng, DanboEngine):
             key = (R, G, int(N_samples), int(N_importance), cams is not None, eng.cfg['use_volume_near_far'],
-                   float(eng.cfg['density_scale']), tuple(eng.cfg['density_act']))
+                   float(eng.cfg['density_scale']), tuple(eng.cfg['density_act']), tuple(sorted(part.items())))
             return self._graphs.run([eng] if fine is None else [eng, fine], key, chain, ray_batch, skts_g, bones_g, cyls_g, cams)
         return chain(ray_batch, skts_g, bones_g, cyls_g, cams)
 
@@ -299,7 +313,8 @@ class RayCaster(nn.Module):
     @torch.no_grad()
     def render_rays_whole(self, ray_batch, chunk, N_samples=None, kp_batch=None, skts=None, cyls=None, bones=None, cams=None,
                           lindisp=False, perturb=0., N_importance=0, raw_noise_std=0., ray_noise_std=0., N_uniques=1,
-                          preproc_kwargs={}, fwd_type='', rays=None, near_far0=None, **kwargs):
+                          preproc_kwargs={}, fwd_type='', rays=None, near_far0=None, render_confd=False, render_entropy=False,
+                          part_valid_only=False, **kwargs):
         """`trainer.batchify_rays`' loop over `chunk`-ray casts as ONE cast of all rays, when that is the same computation, else
         None (the caller loops).  It is the same when every ray belongs to one pose (so a chunk's N_uniques = 1 whatever the
         chunking) and the engine is the DANBO engine: every stage is per ray or per sample except the cylinder bounds' nan-mean
@@ -310,6 +325,7 @@ class RayCaster(nn.Module):
         eng, fine = self._engines(preproc_kwargs)
         if not isinstance(eng, DanboEngine) or N_samples > 256 or N_importance > 64:
             return None
+        part = self._part_kwargs(eng, render_confd, render_entropy, part_valid_only)
         skts_g, bones_g, cyls_g = skts[:1].contiguous(), bones[:1].contiguous(), cyls[:1].contiguous()
         chunk = int(chunk)
         R = rays[0].shape[0] if rays is not None else ray_batch.shape[0]
@@ -329,7 +345,7 @@ class RayCaster(nn.Module):
             if eng.cfg['use_volume_near_far']:
                 ops.near_far_boxes(rays_o, rays_d, skts_g, eng.align, eng.axis_scale, near, far)
             return self._render(eng, fine, rays_o, rays_d, skts_g, bones_g, cyls_g, None if cams is None else cams[a:b], N_samples,
-                                N_importance, near_far=(near, far))
+                                N_importance, near_far=(near, far), **part)
 
         if R <= sub:
             return cast(0, R)

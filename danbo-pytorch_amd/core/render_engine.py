@@ -41,32 +41,71 @@ class RenderEngine:
     def _network_pass(self, rays_o, rays_d, skts, bones, cam_idx, z, bounds, dense, lazy, tag):
         """this engine's network on the samples at depths z [R, n], all inside bounds = (near, far); tag: "coarse" / "fine"
         -> (raw [R,n,4], in-volume bits or None, per-ray empty-space raw or None, extras for keep=True).  With bits, raw rows
-        whose word is 0 are unwritten: the composite reads the empty-space raw for them."""
+        whose word is 0 are unwritten: the composite reads the empty-space raw for them.  The DANBO engine also takes
+        want_confd=True: its extras then hold what a part map reads ("part": forward_samples' extras)."""
         raise NotImplementedError
 
+    @staticmethod
+    def _part_mode(part_map):
+        if part_map not in (None, "confd", "entropy"):
+            raise ValueError(f"part_map must be None, 'confd' or 'entropy', not {part_map!r}")
+        return part_map
+
+    def _part_exact_culled(self, act):
+        """a part map may run on the culled path: samples outside every volume have no logits there, which is exact if and only
+        if their weight is exactly +0 -- relu density and an empty-space density <= 0 (statement (a) of _flat_rays_ok)"""
+        return act[0] == "relu" and bool(getattr(self, "empty_density_le0", False))
+
+    @staticmethod
+    def _part_colors(ex, n_samples, mode, valid_only, dense):
+        """colours [R, n, 3] of one pass's samples from the logits K2 left in forward_samples' extras `ex` (rows of the samples
+        outside every volume stay unwritten on the culled path) -> (colours, in-volume words the composite skips by, or None)"""
+        confd = ex["confd_rows"]
+        R = ex["valid_bits"].numel() // n_samples
+        rgb = torch.empty(R, n_samples, 3, device=confd.device, dtype=torch.float32)
+        ops.part_colors(confd, mode, rgb, ex["list"], ex["count"], bits=ex["valid_bits"], valid_only=valid_only)
+        return rgb, (None if dense else ex["valid_bits"])
+
     def render_two_net(self, fine, rays_o, rays_d, skts, bones, cyls, cam_idx=None, N_samples=None, N_importance=None,
-                       chunk=4096, near_far=None, dense=False, keep=False):
+                       chunk=4096, near_far=None, dense=False, keep=False, part_map=None, part_valid_only=False):
         """The hierarchical render of a caster with a separate fine network (single_net = False, reference raycasters.py:330-377):
         this engine's network on the S coarse samples and their composite (rgb0 ...); the two-network pdf (is_only=False) for the
         Sf importance depths; `fine` -- the fine network's engine -- on ALL S + Sf samples in sorted order, composited as they
         are: coarse and fine raw are never merged.  The bounds are this (the coarse) engine's, as the reference's
-        use_volume_near_far.  No rays of constants here: the fine pass reads z_sorted of every ray, so every ray is resampled."""
+        use_volume_near_far.  No rays of constants here: the fine pass reads z_sorted of every ray, so every ray is resampled.
+        part_map / part_valid_only: as DanboEngine.render -- rgb0 is the part map of the coarse network's logits under the coarse
+        weights, rgb_map that of the FINE network's logits on the S + Sf sorted samples under the final weights (no merge); dense
+        unless both networks allow the culled path."""
         S, Sf, B, act = self._sampling(N_samples, N_importance)
         self.refresh()
         fine.refresh()
+        part = self._part_mode(part_map)
+        if part and not (self._part_exact_culled(act) and fine._part_exact_culled(act)):
+            dense = True
         lazy = not dense and not keep
+        pkw = dict(want_confd=True) if part else {}        # (only an engine with an assignment net knows the argument)
         near, far = self.near_far(rays_o, rays_d, cyls, skts, 0.0, 1.0, chunk) if near_far is None else near_far
         z = ops.coarse_samples(near, far, S)
-        raw, bits, empty, ex = self._network_pass(rays_o, rays_d, skts, bones, cam_idx, z, (near, far), dense, lazy, "coarse")
+        raw, bits, empty, ex = self._network_pass(rays_o, rays_d, skts, bones, cam_idx, z, (near, far), dense, lazy, "coarse", **pkw)
         if self.fuse_resample and S <= 64 and Sf <= 64:
             out0, z_all, z_fine, order = ops.composite_importance(raw, z, rays_d, Sf, B, bits=bits, raw_empty=empty,
-                                                                  want_weights=keep, two_net=True, act=act)
+                                                                  want_weights=keep or bool(part), two_net=True, act=act)
         else:
             out0 = ops.composite(raw, z, rays_d, B, bits=bits, raw_empty=empty, act=act)
             z_all, z_fine, order = ops.importance_samples(z, out0["weights"], Sf, two_net=True)
-        raw_f, bits_f, empty_f, ex_f = fine._network_pass(rays_o, rays_d, skts, bones, cam_idx, z_all, (near, far), dense, lazy, "fine")
+        raw_f, bits_f, empty_f, ex_f = fine._network_pass(rays_o, rays_d, skts, bones, cam_idx, z_all, (near, far), dense, lazy, "fine",
+                                                          **pkw)
         out = ops.composite(raw_f, z_all, rays_d, B, bits=bits_f, raw_empty=empty_f, act=act)
+        pex, pex_f = ex.pop("part", None), ex_f.pop("part", None)
+        if part:
+            col, cb = self._part_colors(pex, S, part, part_valid_only, dense)
+            ops.composite_colors(col, out0["weights"], bits_a=cb, out=out0["rgb_map"])
+            col_f, cb_f = self._part_colors(pex_f, S + Sf, part, part_valid_only, dense)
+            ops.composite_colors(col_f, out["weights"], bits_a=cb_f, out=out["rgb_map"])
         ret = self.frame_result(out, out0)
+        if keep and part:
+            ret.update(confd_coarse=pex["confd_rows"], confd_fine=pex_f["confd_rows"], list_coarse=pex["list"],
+                       list_fine=pex_f["list"])
         if keep:
             ret.update(near=near, far=far, z_coarse=z, raw_coarse=raw, weights_coarse=out0["weights"], z_fine=z_fine,
                        z_sorted=z_all, sorted_idxs=order, raw_fine=raw_f, **ex, **ex_f)
@@ -164,22 +203,26 @@ class DanboEngine(RenderEngine):
         most sum_c |rgb_w_c| * hidden_c + |rgb_b| -- finite and far from overflow means no inf - inf, no NaN.  Then a ray that
         cannot meet a volume is a ray of constants."""
         cfg = self.cfg
-        if self.mlp_mode != "f16split":
-            return False
         ec = self.empty_consts
+        if self.mlp_mode != "f16split":
+            self.empty_density_le0 = bool((ec[128] / float(cfg["density_scale"]) <= 0).item())
+            return False
         Cpe = 3 * (1 + 2 * cfg["multires_views"])
         vmax = 1.0 if cfg["view_type"] == "relray" else ops.RAY_FLAT_VMAX
         a_max = self.wrt[:Cpe].abs().sum(0) * vmax
         if self.code_table is not None:
             a_max = a_max + self.code_table.abs().max(0).values
         elif self.wrt.shape[0] > Cpe:
+            self.empty_density_le0 = bool((ec[128] / float(cfg["density_scale"]) <= 0).item())
             return False
         else:
             a_max = a_max + self.views_b16.abs()
         hidden = ec[:128].abs() + a_max
         logit = ((self.rgb_w.abs() * hidden[None, :]).sum(-1) + self.rgb_b.abs()).max()
-        ok = (ec[128] / float(cfg["density_scale"]) <= 0) & (logit < 1e30)
-        return bool(ok.item())
+        le0 = ec[128] / float(cfg["density_scale"]) <= 0
+        # statement (a) alone is what a part map's culled path needs (render(part_map=...)): kept as its own attribute
+        self.empty_density_le0, ok = torch.stack([le0, le0 & (logit < 1e30)]).tolist()
+        return ok
 
     @staticmethod
     def _equalized(p):
@@ -377,9 +420,26 @@ class DanboEngine(RenderEngine):
         return near, far
 
     def render(self, rays_o, rays_d, skts, bones, cyls, cam_idx=None, N_samples=None, N_importance=None,
-               chunk=4096, near_far=None, dense=False, keep=False):
+               chunk=4096, near_far=None, dense=False, keep=False, part_map=None, part_valid_only=False):
+        """The two-pass render of one network (reference raycasters.py:245-396, eval) -> frame_result's dict.
+
+        part_map: None | 'confd' | 'entropy' -- rgb_map and rgb0 become the bone-assignment map instead of the colour image
+        (raw2outputs with render_confd / render_entropy, reference nerf.py:306-313): the colour of a sample is the palette colour
+        of the bone with the largest assignment logit ('confd') or blue -> red by the entropy of the softmax over the bones
+        ('entropy'), composited with the render's own weights; every other output is bit for bit that of the plain render.
+        part_valid_only: only the bones whose volume holds the sample take part (what the network actually blends); a sample
+        inside no volume gets colour 0.  Both passes then ask K2 for all 24 logits, the coarse composite hands back its weights,
+        and two small launches per pass (ops.part_colors, ops.composite_colors) overwrite rgb0 / rgb_map of the listed rays.
+        Samples outside every volume have no logits on the culled path; leaving them out is exact if and only if their weight is
+        exactly +0, which holds for relu density with an empty-space density <= 0 (`empty_density_le0`).  Otherwise -- softplus,
+        or a positive empty-space density -- a part-map render runs dense=True, so that every sample has logits.
+        keep=True additionally returns what the colouring read: confd_coarse / confd_fine (K2's rows) and list_coarse /
+        list_fine (row -> sample; None when dense), beside count_*, valid_bits and valid_bits_fine."""
         S, Sf, B, act = self._sampling(N_samples, N_importance)
         self.refresh()
+        part = self._part_mode(part_map)
+        if part and not self._part_exact_culled(act):
+            dense = True
         fused = S <= 64 and Sf <= 64
         lazy = not dense and not keep      # skip the raw pre-fill: consumers read raw_empty where bits == 0
         # lazy: nobody outside this function sees z_fine, the sorted order or the per-ray view constants.  If the weights allow it
@@ -403,37 +463,47 @@ class DanboEngine(RenderEngine):
         flat = None
         vols = self.volumes(bones)
         if flat_mode:
-            flat = ops.flat_rays(ray_mask[1], ray_mask[3], S, Sf, want_weights=not fused, cnt=counts[2:3])
+            flat = ops.flat_rays(ray_mask[1], ray_mask[3], S, Sf, want_weights=not fused or bool(part), cnt=counts[2:3])
             view = self.view_constants(rays_d, skts, cam_idx, flat["ray_list"], flat["ray_count"])
         else:
             view = self.view_constants(rays_d, skts, cam_idx)
         if ray_mask is not None:
             ray_mask = ray_mask[:3]
         raw, ex = self.forward_samples(rays_o, rays_d, skts, bones, cam_idx, z=z, dense=dense, volumes=vols, view=view,
-                                       fill=not lazy, ray_mask=ray_mask, count=counts[0:1])
+                                       fill=not lazy, ray_mask=ray_mask, count=counts[0:1], want_confd=bool(part))
         if fused:
             out0, z_all, z_fine, order = ops.composite_importance(
                 raw, z, rays_d, Sf, B, bits=ex["valid_bits"] if lazy else None, raw_empty=view[1] if lazy else None,
-                want_weights=keep, flat=flat, act=act)
+                want_weights=keep or bool(part), flat=flat, act=act)
         else:
             out0 = ops.composite(raw, z, rays_d, B, bits=ex["valid_bits"] if lazy else None, raw_empty=view[1] if lazy else None,
                                  flat=flat, act=act)
             z_all, z_fine, order = ops.importance_samples(z, out0["weights"], Sf, flat=flat)
         raw_f, ex_f = self.forward_samples(rays_o, rays_d, skts, bones, cam_idx, z=z_fine, dense=dense,
                                            volumes=vols, view=view, fill=not lazy,
-                                           ray_mask=ray_mask, count=counts[1:2])
+                                           ray_mask=ray_mask, count=counts[1:2], want_confd=bool(part))
         out = ops.composite_merged(raw, raw_f, order, z_all, rays_d, B, bits_a=ex["valid_bits"] if lazy else None,
                                    bits_b=ex_f["valid_bits"] if lazy else None, raw_empty=view[1] if lazy else None,
                                    want_raw=keep, flat=flat, act=act)
+        if part:
+            # the colours of both passes' samples, then the two maps over the render's own weights: rgb0 through the coarse
+            # order, rgb_map through the sorted order.  The rows of the rays of constants hold +0 already, which is their map.
+            col, cb = self._part_colors(ex, S, part, part_valid_only, dense)
+            col_f, cb_f = self._part_colors(ex_f, Sf, part, part_valid_only, dense)
+            ops.composite_colors(col, out0["weights"], bits_a=cb, flat=flat, out=out0["rgb_map"])
+            ops.composite_colors(col, out["weights"], col_f, order, cb, cb_f, flat=flat, out=out["rgb_map"])
         ret = self.frame_result(out, out0)
         if keep:
             ret.update(near=near, far=far, z_coarse=z, raw_coarse=raw, weights_coarse=out0["weights"], z_fine=z_fine,
                        z_sorted=z_all, sorted_idxs=order, raw_fine=raw_f, raw_sorted=out.get("raw_sorted"),
                        count_coarse=ex["count"], count_fine=ex_f["count"], valid_bits=ex["valid_bits"])
+            if part:
+                ret.update(confd_coarse=ex["confd_rows"], confd_fine=ex_f["confd_rows"], list_coarse=ex["list"],
+                           list_fine=ex_f["list"], valid_bits_fine=ex_f["valid_bits"])
         return ret
 
     # ------------------------------------------------------------------ one network pass of render_two_net (single_net = False)
-    def _network_pass(self, rays_o, rays_d, skts, bones, cam_idx, z, bounds, dense, lazy, tag):
+    def _network_pass(self, rays_o, rays_d, skts, bones, cam_idx, z, bounds, dense, lazy, tag, want_confd=False):
         """Each pass culls with its own network's volumes (the fine network's axis_scale is its own parameter: a mask from the coarse
         boxes could drop fine samples inside a fine volume).  lazy (dense=False, keep=False) leaves the raw rows outside every
         volume unwritten, the composite reading this network's empty-space raw for them -- bit for bit the filled result."""
@@ -441,6 +511,9 @@ class DanboEngine(RenderEngine):
         mask = None if dense else ops.ray_bone_mask(rays_o, rays_d, skts, self.align, self.axis_scale, *bounds)
         view = self.view_constants(rays_d, skts, cam_idx)
         raw, ex = self.forward_samples(rays_o, rays_d, skts, bones, cam_idx, z=z, dense=dense, volumes=self.volumes(bones), view=view,
-                                       fill=not lazy, ray_mask=mask)
+                                       fill=not lazy, ray_mask=mask, want_confd=want_confd)
         bits, empty = (ex["valid_bits"], view[1]) if lazy else (None, None)
-        return raw, bits, empty, {"count_" + tag: ex["count"], "valid_bits" + ("_fine" if tag == "fine" else ""): ex["valid_bits"]}
+        extras = {"count_" + tag: ex["count"], "valid_bits" + ("_fine" if tag == "fine" else ""): ex["valid_bits"]}
+        if want_confd:
+            extras["part"] = ex
+        return raw, bits, empty, extras

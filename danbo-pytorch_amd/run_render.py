@@ -48,8 +48,12 @@ def config_parser():
     p.add_argument('--mesh_render', nargs='?', const='normal', default=None, choices=['normal', 'color', 'flat'],
                    help='with --render_mesh: the turntable of every mesh (render_mesh.py) straight from the device tensors')
     p.add_argument('--mesh_render_res', nargs=2, type=int, default=[512, 512], help='(H, W) of the turntable frames')
-    p.add_argument('--render_confd', action='store_true')
-    p.add_argument('--render_entropy', action='store_true')
+    p.add_argument('--render_confd', action='store_true', help='image.npy holds the part map: every sample coloured by the bone '
+                   'with the largest assignment logit')
+    p.add_argument('--render_entropy', action='store_true', help='image.npy holds the entropy of the bone assignment, blue (one '
+                   'bone) to red (uniform); --render_confd wins when both are given')
+    p.add_argument('--part_valid_only', action='store_true', help='with --render_confd / --render_entropy: only the bones whose '
+                   'volume holds the sample take part')
     p.add_argument('--selected_idxs', nargs='+', type=int, default=None)
     p.add_argument('--selected_framecode', type=int, default=None)
     p.add_argument('--n_bullet', type=int, default=10)
@@ -308,7 +312,8 @@ def run_render(argv=None):
                     normals=args.mesh_normals, colors=args.mesh_colors, turntable=args.mesh_render,
                     turntable_res=tuple(args.mesh_render_res))
         return None
-    render_kwargs = dict(render_kwargs, render_confd=args.render_confd, render_entropy=args.render_entropy)
+    render_kwargs = dict(render_kwargs, render_confd=args.render_confd, render_entropy=args.render_entropy,
+                         part_valid_only=args.part_valid_only)
     rgbs, _, accs, _, bboxes = render_path(render_kwargs=render_kwargs, chunk=nerf_args.chunk, ext_scale=nerf_args.ext_scale,
                                            ret_acc=True, white_bkgd=args.white_bkgd, **tensor_data)
     scores = None
