@@ -13,7 +13,8 @@ is skipped.  A new entry point needs its declaration in the header and its imple
 The header is $DANBO_HIP_HEADER, else danbo_hip.h beside the library, else include/danbo_hip.h of the source tree.  The
 rasteriser's two entries stand in danbo_raster.h beside it and are bound the same way into RASTER_SIGNATURES / RASTER_RESTYPES /
 RASTER_C (tables of their own: SIGNATURES and C are the statement of danbo_hip.h alone); the two entries of the bone-assignment maps
-stand in danbo_partmap.h and are bound into PARTMAP_SIGNATURES / PARTMAP_RESTYPES.  `lib()` refuses
+stand in danbo_partmap.h and are bound into PARTMAP_SIGNATURES / PARTMAP_RESTYPES, the two of the image metrics in
+danbo_metrics.h into METRICS_SIGNATURES / METRICS_RESTYPES.  `lib()` refuses
 a library whose danbo_abi_version() is not the header's DANBO_ABI_VERSION (a stale build).
 
 The library is the only compute backend of this package: there is NO PyTorch/CPU fallback.  `lib()` raises if the shared object is
@@ -234,6 +235,17 @@ if _p_structs or _p_constants or set(_p_functions) & (set(_functions) | set(_r_f
     raise HeaderError(f"{PARTMAP_HEADER_PATH} declares a struct, a constant, or a name another header declares")
 PARTMAP_SIGNATURES = {name: argtypes for name, (_, argtypes) in _p_functions.items()}
 PARTMAP_RESTYPES = {name: restype for name, (restype, _) in _p_functions.items()}
+
+# ---- the image metrics' entries (include/danbo_metrics.h, beside danbo_hip.h), bound the same way
+METRICS_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "danbo_metrics.h")
+if not os.path.exists(METRICS_HEADER_PATH):
+    raise RuntimeError(f"{METRICS_HEADER_PATH} not found (the binding of the image metrics is derived from it, it lies beside danbo_hip.h)")
+with open(METRICS_HEADER_PATH) as _f:
+    _m_functions, _m_structs, _m_constants = parse_header(_f.read())
+if _m_structs or _m_constants or set(_m_functions) & (set(_functions) | set(_r_functions) | set(_p_functions)):
+    raise HeaderError(f"{METRICS_HEADER_PATH} declares a struct, a constant, or a name another header declares")
+METRICS_SIGNATURES = {name: argtypes for name, (_, argtypes) in _m_functions.items()}
+METRICS_RESTYPES = {name: restype for name, (restype, _) in _m_functions.items()}
 ANERF_MAX_D = C.DANBO_ANERF_MAX_D
 
 # ---- training step: the state_dict key of every slot of DanboTrainModel.p / .g (enum DanboTrainTensor; the names are Python's)
@@ -264,10 +276,10 @@ def lib():
                 f"{LIB_PATH} not found: build it with `make -C danbo-pytorch_amd/csrc` "
                 "(or __graft_entry__.build()).  There is no CPU / PyTorch fallback.")
         l = ctypes.CDLL(LIB_PATH)
-        for name, argtypes in {**SIGNATURES, **RASTER_SIGNATURES, **PARTMAP_SIGNATURES}.items():
+        for name, argtypes in {**SIGNATURES, **RASTER_SIGNATURES, **PARTMAP_SIGNATURES, **METRICS_SIGNATURES}.items():
             fn = getattr(l, name)
             fn.argtypes = argtypes
-            fn.restype = RESTYPES.get(name) or RASTER_RESTYPES.get(name) or PARTMAP_RESTYPES[name]
+            fn.restype = RESTYPES.get(name) or RASTER_RESTYPES.get(name) or PARTMAP_RESTYPES.get(name) or METRICS_RESTYPES[name]
         if l.danbo_abi_version() != C.DANBO_ABI_VERSION:
             raise RuntimeError(f"{LIB_PATH} has ABI version {l.danbo_abi_version()}, {HEADER_PATH} declares {C.DANBO_ABI_VERSION}: "
                                "the library is stale, rebuild it with `make -C danbo-pytorch_amd/csrc`")

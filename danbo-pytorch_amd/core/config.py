@@ -45,6 +45,8 @@ _FLAGS = [
     ("i_print", int, 100), ("dataset_type", str, "synthetic"),
     # this build's array sources (core/load_data.py): the reference's HDF5 dataset types are not readable here
     ("syn_poses", int, 8), ("syn_cams", int, 4), ("syn_res", int, 64), ("syn_seed", int, 0), ("syn_rest_scale", float, 0.48),
+    # validation frames stay on the device and are scored there (evaluation_helpers.evaluate_metric_device)
+    ("eval_device", bool, False),
 ]
 
 

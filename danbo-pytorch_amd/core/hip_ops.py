@@ -1000,3 +1000,59 @@ def rasterize_mesh(verts, faces, attr=None, mode="normal", views=None, half_exte
           RASTER_MODES[mode], _p(views), n, float(half_extent), H, W, _p(bg), _p(ws), _p(out.get("rgb")), _p(out.get("depth")),
           _p(out.get("tri_id")), _stream())
     return out
+
+
+# -------------------------------------------------------------------------------------- image metrics
+METRICS_WIN = 11           # ssim_map's default window (evaluation_helpers._gauss)
+_METRIC_WINDOWS = {}
+_METRIC_WORKSPACES = {}
+
+
+def metrics_window(device):
+    """The one SSIM window, evaluation_helpers._gauss(), on `device` (cached): the kernel is handed ssim_map's own weights."""
+    key = str(device)
+    if key not in _METRIC_WINDOWS:
+        from .utils.evaluation_helpers import _gauss
+        _METRIC_WINDOWS[key] = _gauss(METRICS_WIN).to(device=device, dtype=torch.float32).contiguous()
+    return _METRIC_WINDOWS[key]
+
+
+def image_metrics(pred, gt, mask_a=None, mask_b=None, boxes=None, want_map=False):
+    """Squared error and SSIM of frames against the ground truth, summed per image on the device (danbo_image_metrics; the scoring
+    of evaluation_helpers.evaluate_in_boxes / evaluate_metric).  pred, gt [N,H,W,3] float32; mask_a, mask_b [N,H,W] (or [N,H,W,1])
+    float weights; boxes [N,4] int32 x0, y0, x1, y1 (half open, clamped to the image; None: whole images) -- SSIM is that of the
+    crop, zero padded.  -> dict(sums=[N,8] float32: S se, S ssim, S se a, S ssim a, S a, S se b, S ssim b, S b (the slots of a mask
+    that is None: 0), ssim_map=[N,H,W,3] inside the boxes (0 outside) or None).  Two launches on the current stream, no
+    synchronisation; the same bits on every call.  The window is cached per device, the workspace per device, size and stream."""
+    for t, name in ((pred, "pred"), (gt, "gt"), (mask_a, "mask_a"), (mask_b, "mask_b"), (boxes, "boxes")):
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"{name}: expected a CUDA/HIP tensor -- libdanbo_hip has no CPU fallback")
+    if pred.dim() != 4 or pred.shape[-1] != 3 or pred.shape != gt.shape:
+        raise ValueError("image_metrics: pred and gt must be [N, H, W, 3] tensors of one shape")
+    pred, gt = _f32(pred, "pred"), _f32(gt, "gt")
+    pred, gt = (t.clone() if t.data_ptr() % 16 else t for t in (pred, gt))        # (a slice of a stack may start anywhere)
+    N, H, W = pred.shape[:3]
+    dev = pred.device
+
+    def mask(m, name):
+        if m is None:
+            return None
+        if m.numel() != N * H * W:
+            raise ValueError(f"image_metrics: {name} must be [N, H, W] (or [N, H, W, 1])")
+        return _f32(m, name).reshape(N, H, W)
+    mask_a, mask_b = mask(mask_a, "mask_a"), mask(mask_b, "mask_b")
+    if boxes is not None:
+        if boxes.dtype != torch.int32 or tuple(boxes.shape) != (N, 4):
+            raise ValueError("image_metrics: boxes must be an [N, 4] int32 tensor")
+        boxes = boxes.contiguous()
+    n_bytes = _hip.lib().danbo_image_metrics_workspace_bytes(N, H, W)
+    if n_bytes == 0:
+        raise _hip.HipError(f"image_metrics: unsupported size {N} x {H} x {W} (height and width 1 .. 4096)")
+    key = (str(dev), n_bytes, torch.cuda.current_stream().cuda_stream)
+    if key not in _METRIC_WORKSPACES:
+        _METRIC_WORKSPACES[key] = torch.empty(n_bytes, device=dev, dtype=torch.uint8)
+    sums = torch.empty(N, 8, device=dev, dtype=torch.float32)
+    ssim = torch.zeros(N, H, W, 3, device=dev, dtype=torch.float32) if want_map else None
+    _call("danbo_image_metrics", _p(pred), _p(gt), _p(mask_a), _p(mask_b), _p(boxes), N, H, W, _p(metrics_window(dev)), METRICS_WIN,
+          _p(_METRIC_WORKSPACES[key]), _p(sums), _p(ssim), _stream())
+    return dict(sums=sums, ssim_map=ssim)

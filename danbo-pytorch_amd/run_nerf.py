@@ -23,16 +23,17 @@ from core.config import config_parser, parse_args  # noqa: E402,F401
 from core.load_data import load_data  # noqa: E402
 from core.raycasters import create_raycaster  # noqa: E402
 from core.trainer import Trainer, render  # noqa: E402
-from core.utils.evaluation_helpers import evaluate_metric  # noqa: E402
+from core.utils.evaluation_helpers import evaluate_metric, evaluate_metric_device  # noqa: E402
 from core.utils.ray_utils import kp_to_valid_rays  # noqa: E402
 
 
 def render_path(render_poses, hwf, chunk, render_kwargs, centers=None, kp=None, skts=None, cyls=None, bones=None, gt_imgs=None,
                 bg_imgs=None, bg_indices=None, cams=None, subject_idxs=None, render_factor=0, white_bkgd=False, ret_acc=False,
-                ext_scale=0.00035, base_bg=1.0):
+                ext_scale=0.00035, base_bg=1.0, device_out=False):
     """One image per camera in `render_poses`: only the pixels inside the 2-D box of the pose's bounding cylinder are cast,
     the rest of the image is the background (`bg_imgs[bg_indices[i]]` resized, white, or black).  Pose tensors with fewer
-    entries than cameras are cycled (`i % n`).  -> rgbs [N,H,W,3], disps [N,H,W,1], accs, valid_idxs, bboxes"""
+    entries than cameras are cycled (`i % n`).  -> rgbs [N,H,W,3], disps [N,H,W,1], accs, valid_idxs, bboxes: numpy arrays, one
+    device-to-host copy per frame; with device_out the stacked DEVICE tensors (nan_to_num applied there), nothing copied."""
     H, W, focal = hwf
     if render_factor != 0:
         H, W = H // render_factor, W // render_factor
@@ -48,6 +49,7 @@ def render_path(render_poses, hwf, chunk, render_kwargs, centers=None, kp=None, 
         y = x[i % x.shape[0]:i % x.shape[0] + 1] if x.shape[0] > 1 else x
         return y.to(dev).expand(n_rays, *x.shape[1:])
 
+    out = (lambda x: x) if device_out else (lambda x: x.cpu().numpy())      # a frame stays where it is, or crosses to the host
     rgbs, disps, accs = [], [], []
     for i, c2w in enumerate(render_poses):
         h = H if isinstance(H, int) else int(H[i])
@@ -67,12 +69,13 @@ def render_path(render_poses, hwf, chunk, render_kwargs, centers=None, kp=None, 
                          subject_idxs=per_image(subject_idxs, i, n), bones=per_image(bones, i, n), **render_kwargs)
             rgb_img[idx] = ret['rgb_map'] + (1. - ret['acc_map'][..., None]) * rgb_img[idx]
             disp_img[idx], acc_img[idx] = ret['disp_map'], ret['acc_map']
-        rgbs.append(rgb_img.view(h, w, 3).cpu().numpy())
-        disps.append(disp_img.view(h, w, 1).cpu().numpy())
+        rgbs.append(out(rgb_img.view(h, w, 3)))
+        disps.append(out(disp_img.view(h, w, 1)))
         if ret_acc:
-            accs.append(acc_img.view(h, w, 1).cpu().numpy())
-    rgbs, disps = np.stack(rgbs, 0), np.nan_to_num(np.stack(disps, 0), nan=0.)
-    return rgbs, disps, (np.stack(accs, 0) if ret_acc else accs), valid_idxs, bboxes
+            accs.append(out(acc_img.view(h, w, 1)))
+    stack, nan_to_num = (torch.stack, torch.nan_to_num) if device_out else (np.stack, np.nan_to_num)
+    rgbs, disps = stack(rgbs, 0), nan_to_num(stack(disps, 0), nan=0.)
+    return rgbs, disps, (stack(accs, 0) if ret_acc else accs), valid_idxs, bboxes
 
 
 def render_testset(poses, hwf, args, render_kwargs, kps=None, skts=None, cyls=None, cams=None, bones=None, subject_idxs=None,
@@ -85,15 +88,18 @@ def render_testset(poses, hwf, args, render_kwargs, kps=None, skts=None, cyls=No
     rgbs, disps, _, valid_idxs, _ = render_path(poses, hwf, args.chunk // 8, render_kwargs, bg_imgs=bg_imgs, bg_indices=bg_indices,
                                                 centers=centers, kp=kps, skts=skts, cyls=cyls, bones=bones, cams=cams,
                                                 subject_idxs=subject_idxs, render_factor=args.render_factor,
-                                                ext_scale=args.ext_scale, white_bkgd=args.white_bkgd)
+                                                ext_scale=args.ext_scale, white_bkgd=args.white_bkgd,
+                                                device_out=getattr(args, "eval_device", False))
     caster.train(was_training)
     if not eval_metrics:
         return rgbs, disps
     if gt_masks is not None and gt_masks.sum() < 1:
         gt_masks = None
-    metrics = evaluate_metric(rgbs, gt_imgs, disps, gt_masks, valid_idxs, poses, kps, hwf, centers, args.ext_scale,
-                              vid_base=vid_base, eval_postfix=eval_postfix, eval_both=eval_both and gt_masks is not None,
-                              white_bkgd=args.white_bkgd, render_factor=args.render_factor)
+    # --eval_device: the frames are device tensors and are scored where they are (only the sums cross to the host)
+    score = evaluate_metric_device if getattr(args, "eval_device", False) else evaluate_metric
+    metrics = score(rgbs, gt_imgs, disps, gt_masks, valid_idxs, poses, kps, hwf, centers, args.ext_scale, vid_base=vid_base,
+                    eval_postfix=eval_postfix, eval_both=eval_both and gt_masks is not None, white_bkgd=args.white_bkgd,
+                    render_factor=args.render_factor)
     return metrics, rgbs, disps
 
 
@@ -116,7 +122,17 @@ def sync_replicas(module, src=0):
 def validate(args, render_data, render_kwargs_test, device, vid_base):
     t = lambda x: torch.tensor(np.ascontiguousarray(x)).to(device)  # noqa: E731
     gt, fg, bgs, bg_idx = render_data["imgs"], render_data["fgs"], render_data["bgs"], render_data.get("bg_idxs")
-    masked = gt * fg + (1 - fg) * (bgs[bg_idx] if bg_idx is not None else bgs)
+    if getattr(args, "eval_device", False):
+        # the validation set's ground truth, masks and backgrounds are uploaded once and kept on the device
+        kept = render_data.setdefault("_eval_device", {})
+        if not kept:
+            d_bgs = t(bgs).float()
+            kept.update(fg=t(fg).float(), bgs=d_bgs)
+            bg = d_bgs[t(bg_idx).long()] if bg_idx is not None else d_bgs
+            kept["masked"] = t(gt).float() * kept["fg"] + (1 - kept["fg"]) * bg
+        masked, fg, bgs = kept["masked"], kept["fg"], kept["bgs"]
+    else:
+        masked = gt * fg + (1 - fg) * (bgs[bg_idx] if bg_idx is not None else bgs)
     H, W, focals = render_data["hwf"]
     hwf = (int(H[0]), int(W[0]), focals.astype(np.float32))
     cams = t(render_data["cam_idxs"]) if args.opt_framecode else None

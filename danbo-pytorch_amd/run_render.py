@@ -23,7 +23,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from core.config import config_parser as nerf_config_parser, txt_to_argstring  # noqa: E402
 from core.load_data import PoseImageDataset, generate_bullet_time, get_dataset  # noqa: E402
 from core.raycasters import create_raycaster  # noqa: E402
-from core.utils.evaluation_helpers import evaluate_in_boxes  # noqa: E402
+from core.utils.evaluation_helpers import evaluate_in_boxes, evaluate_in_boxes_device  # noqa: E402
 from core.utils.mesh_io import write_ply  # noqa: E402
 from core.utils.mesh_render import render_turntable  # noqa: E402
 from core.utils.skeleton_utils import get_smpl_l2ws  # noqa: E402
@@ -61,6 +61,8 @@ def config_parser():
     p.add_argument('--outputdir', type=str, default='render_output/')
     p.add_argument('--runname', type=str, required=True)
     p.add_argument('--eval', action='store_true', help='PSNR / SSIM inside the bounding boxes against the data images')
+    p.add_argument('--eval_device', action='store_true', help='with --eval: the frames stay on the device and are scored there '
+                   '(with --no_save only the sums of the scores cross to the host)')
     p.add_argument('--no_save', action='store_true')
     return p
 
@@ -254,9 +256,9 @@ def to_tensors(data, device):
     return out
 
 
-def evaluate_metric(rgbs, accs, bboxes, gt_dict, basedir):
-    scores = evaluate_in_boxes(rgbs, accs, bboxes, gt_dict['gt_paths'], gt_dict['gt_mask_paths'], gt_dict['bg_imgs'],
-                               gt_dict['bg_indices'])
+def evaluate_metric(rgbs, accs, bboxes, gt_dict, basedir, on_device=False):
+    score = evaluate_in_boxes_device if on_device else evaluate_in_boxes
+    scores = score(rgbs, accs, bboxes, gt_dict['gt_paths'], gt_dict['gt_mask_paths'], gt_dict['bg_imgs'], gt_dict['bg_indices'])
     np.save(os.path.join(basedir, 'scores.npy'), scores, allow_pickle=True)
     with open(os.path.join(basedir, 'score_final.txt'), 'w') as f:
         for k, v in scores.items():
@@ -315,10 +317,12 @@ def run_render(argv=None):
     render_kwargs = dict(render_kwargs, render_confd=args.render_confd, render_entropy=args.render_entropy,
                          part_valid_only=args.part_valid_only)
     rgbs, _, accs, _, bboxes = render_path(render_kwargs=render_kwargs, chunk=nerf_args.chunk, ext_scale=nerf_args.ext_scale,
-                                           ret_acc=True, white_bkgd=args.white_bkgd, **tensor_data)
+                                           ret_acc=True, white_bkgd=args.white_bkgd, device_out=args.eval_device, **tensor_data)
     scores = None
     if gt_dict['gt_paths'] is not None and args.eval:
-        scores = evaluate_metric(rgbs, accs, bboxes, gt_dict, basedir)
+        scores = evaluate_metric(rgbs, accs, bboxes, gt_dict, basedir, on_device=args.eval_device)
+    if args.eval_device and not args.no_save:          # the frames leave the device only to be saved
+        rgbs, accs = rgbs.cpu().numpy(), accs.cpu().numpy()
     if not args.no_save:
         np.save(os.path.join(basedir, 'image.npy'), (rgbs * 255).astype(np.uint8))
         np.save(os.path.join(basedir, 'acc.npy'), (accs * 255).astype(np.uint8))

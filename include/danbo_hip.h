@@ -67,7 +67,9 @@ extern "C" {
  * (the density activation: relu or softplus(x - shift), density_type = softplus); danbo_mesh_workspace_bytes, danbo_mesh_count,
  * danbo_mesh_extract (isosurface extraction on the density grid: --render_mesh ends in a mesh); danbo_mesh_normals (vertex normals
  * of the extracted mesh); danbo_part_colors_fwd, danbo_composite_colors_fwd (bone-assignment maps, --render_confd /
- * --render_entropy: declared in danbo_partmap.h beside this file, as the rasteriser's entries are in danbo_raster.h). */
+ * --render_entropy: declared in danbo_partmap.h beside this file, as the rasteriser's entries are in danbo_raster.h);
+ * danbo_image_metrics_workspace_bytes, danbo_image_metrics (PSNR / SSIM sums of rendered frames on the device, --eval_device:
+ * declared in danbo_metrics.h beside this file). */
 #define DANBO_ABI_VERSION 9   /* what danbo_abi_version() of a library built from this header returns; the binding refuses another */
 int danbo_abi_version(void);
 int danbo_device_info(int* cu_count, int* lds_bytes, char* arch, int arch_len);
