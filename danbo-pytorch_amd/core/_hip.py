@@ -14,7 +14,8 @@ The header is $DANBO_HIP_HEADER, else danbo_hip.h beside the library, else inclu
 rasteriser's two entries stand in danbo_raster.h beside it and are bound the same way into RASTER_SIGNATURES / RASTER_RESTYPES /
 RASTER_C (tables of their own: SIGNATURES and C are the statement of danbo_hip.h alone); the two entries of the bone-assignment maps
 stand in danbo_partmap.h and are bound into PARTMAP_SIGNATURES / PARTMAP_RESTYPES, the two of the image metrics in
-danbo_metrics.h into METRICS_SIGNATURES / METRICS_RESTYPES.  `lib()` refuses
+danbo_metrics.h into METRICS_SIGNATURES / METRICS_RESTYPES, the listed-ray cull's in danbo_cull.h into CULL_SIGNATURES /
+CULL_RESTYPES.  `lib()` refuses
 a library whose danbo_abi_version() is not the header's DANBO_ABI_VERSION (a stale build).
 
 The library is the only compute backend of this package: there is NO PyTorch/CPU fallback.  `lib()` raises if the shared object is
@@ -246,6 +247,17 @@ if _m_structs or _m_constants or set(_m_functions) & (set(_functions) | set(_r_f
     raise HeaderError(f"{METRICS_HEADER_PATH} declares a struct, a constant, or a name another header declares")
 METRICS_SIGNATURES = {name: argtypes for name, (_, argtypes) in _m_functions.items()}
 METRICS_RESTYPES = {name: restype for name, (restype, _) in _m_functions.items()}
+
+# ---- the listed-ray cull's entry (include/danbo_cull.h, beside danbo_hip.h), bound the same way
+CULL_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "danbo_cull.h")
+if not os.path.exists(CULL_HEADER_PATH):
+    raise RuntimeError(f"{CULL_HEADER_PATH} not found (the binding of the listed-ray cull is derived from it, it lies beside danbo_hip.h)")
+with open(CULL_HEADER_PATH) as _f:
+    _c_functions, _c_structs, _c_constants = parse_header(_f.read())
+if _c_structs or _c_constants or set(_c_functions) & (set(_functions) | set(_r_functions) | set(_p_functions) | set(_m_functions)):
+    raise HeaderError(f"{CULL_HEADER_PATH} declares a struct, a constant, or a name another header declares")
+CULL_SIGNATURES = {name: argtypes for name, (_, argtypes) in _c_functions.items()}
+CULL_RESTYPES = {name: restype for name, (restype, _) in _c_functions.items()}
 ANERF_MAX_D = C.DANBO_ANERF_MAX_D
 
 # ---- training step: the state_dict key of every slot of DanboTrainModel.p / .g (enum DanboTrainTensor; the names are Python's)
@@ -276,10 +288,11 @@ def lib():
                 f"{LIB_PATH} not found: build it with `make -C danbo-pytorch_amd/csrc` "
                 "(or __graft_entry__.build()).  There is no CPU / PyTorch fallback.")
         l = ctypes.CDLL(LIB_PATH)
-        for name, argtypes in {**SIGNATURES, **RASTER_SIGNATURES, **PARTMAP_SIGNATURES, **METRICS_SIGNATURES}.items():
+        for name, argtypes in {**SIGNATURES, **RASTER_SIGNATURES, **PARTMAP_SIGNATURES, **METRICS_SIGNATURES, **CULL_SIGNATURES}.items():
             fn = getattr(l, name)
             fn.argtypes = argtypes
-            fn.restype = RESTYPES.get(name) or RASTER_RESTYPES.get(name) or PARTMAP_RESTYPES.get(name) or METRICS_RESTYPES[name]
+            fn.restype = (RESTYPES.get(name) or RASTER_RESTYPES.get(name) or PARTMAP_RESTYPES.get(name) or METRICS_RESTYPES.get(name)
+                          or CULL_RESTYPES[name])
         if l.danbo_abi_version() != C.DANBO_ABI_VERSION:
             raise RuntimeError(f"{LIB_PATH} has ABI version {l.danbo_abi_version()}, {HEADER_PATH} declares {C.DANBO_ABI_VERSION}: "
                                "the library is stale, rebuild it with `make -C danbo-pytorch_amd/csrc`")

@@ -135,6 +135,26 @@ def bone_cull(geo, compact=True, cnt=None):
     return bits, lst, cnt
 
 
+def bone_cull_rays(geo, flat, bounds=None, cnt=None, rays_per_wg=0):
+    """bone_cull for the rays flat_rays() listed and for no other (danbo_bone_cull_rays): valid_bits / list / count as bone_cull,
+    the words and the rows of the listed rays only -- the rest of valid_bits stays unwritten.  geo: one pose, with its ray_mask.
+    bounds = (near, far): the coarse pass -- geo.z [R,S] is an OUTPUT, the depths of coarse_samples(near, far, S) for the listed
+    rays; None: geo.z is read (the importance depths).  rays_per_wg: list entries per workgroup (0: the library's choice)."""
+    assert geo.z is not None and geo.ray_mask is not None and geo.z.is_contiguous()
+    bits = torch.empty(geo.M, device=geo.device, dtype=torch.int32)
+    lst = torch.empty(geo.M, device=geo.device, dtype=torch.int32)
+    if cnt is None:
+        cnt = torch.zeros(1, device=geo.device, dtype=torch.int32)
+    assert cnt.dtype == torch.int32 and cnt.numel() == 1 and cnt.is_contiguous()
+    near, far = (None, None) if bounds is None else (_f32(b, "bounds").reshape(-1) for b in bounds)
+    assert near is None or (near.shape[0] == geo.R and far.shape[0] == geo.R)
+    rm = tuple(geo.ray_mask)
+    _call("danbo_bone_cull_rays", *_ray_list(flat), _p(rm[0]), _p(rm[1]), _p(rm[2]), _p(geo.rays_o), _p(geo.rays_d), geo.R, geo.S,
+          geo.G, _p(geo.skts), _p(geo.align), _p(geo.axis_scale), _p(near), _p(far), _p(geo.z), int(rays_per_wg), _p(bits), _p(lst),
+          _p(cnt), _stream())
+    return bits, lst, cnt
+
+
 def ray_bone_mask(rays_o, rays_d, skts, align, axis_scale, t_lo, t_hi, want_flat=False):
     """-> (mask [R] int32, t_lo, t_hi[, flat [R] int32]): bit j of mask[r] clear = no point of ray r between t_lo[r] and t_hi[r]
     can lie inside bone j's volume (conservative slab test, csrc/k_sample.hip:k_ray_bone_mask).  Pass it to

@@ -137,6 +137,10 @@ class DanboEngine(RenderEngine):
         # True: re-order the compacted rows by bone set in front of K2 (k_group.hip).  Off since the end of round 4: K2 gains 2 x 20 us
         # from it, the grouping costs 2 x 27 us and scatters K3's rows (tools/ab_engine_switch.py: 4.734 ms with, 4.712 ms without)
         self.group_rows = False
+        # render(): with rays of constants (one pose, no part map), depths, in-volume words and rows are made for the LISTED rays only,
+        # by one kernel per pass (ops.bone_cull_rays) instead of coarse_samples + bone_cull over every ray: same words, same depths
+        # for those rays, nothing for the others -- which nobody reads ("Rays").  Tests switch it off to compare.
+        self.cull_listed_rays = True
 
     # ------------------------------------------------------------------ derived buffers
     def refresh(self):
@@ -296,20 +300,26 @@ class DanboEngine(RenderEngine):
                                self.code_table, ray_list, ray_count)
 
     def forward_samples(self, rays_o, rays_d, skts, bones, cam_idx=None, z=None, pts=None, dense=False,
-                        want_confd=False, volumes=None, view=None, fill=True, ray_mask=None, count=None):
+                        want_confd=False, volumes=None, view=None, fill=True, ray_mask=None, count=None, listed=None):
         """DANBO.forward on R x S samples -> raw [R,S,4] (+ dict of extras).
 
         dense=False: only samples inside >= 1 bone volume go through K1b/K2/K3; all others take
                      the per-ray empty-space raw (identical values).
         dense=True : every sample goes through every kernel (the reference's executed work).
         ray_mask: ops.ray_bone_mask() of these rays over an interval that holds every depth of z (render: [near, far]).
-        count: zeroed [1] int32 for the row count (render() fills both passes' counters at once)."""
+        count: zeroed [1] int32 for the row count (render() fills both passes' counters at once).
+        listed: (flat, bounds) -- cull only the rays flat_rays() listed (ops.bone_cull_rays; one pose, with ray_mask);
+                bounds = (near, far): z is an uninitialised [R,S] that the cull fills with those rays' coarse depths; None: z is read."""
         self.refresh()
         geo = ops.Geometry(rays_o, rays_d, skts, self.align, self.axis_scale, z=z, pts=pts, ray_mask=ray_mask)
         vols = self.volumes(bones) if volumes is None else volumes
         cview, raw_empty = self.view_constants(geo.rays_d, geo.skts, cam_idx) if view is None else view
         S = geo.S
-        bits, lst, cnt = ops.bone_cull(geo, compact=not dense, cnt=count)
+        if listed is not None:
+            assert not dense and pts is None
+            bits, lst, cnt = ops.bone_cull_rays(geo, listed[0], listed[1], cnt=count)
+        else:
+            bits, lst, cnt = ops.bone_cull(geo, compact=not dense, cnt=count)
         if lst is not None and self.mlp_mode == "f16split" and self.group_rows:
             ops.group_rows(bits, lst, cnt)
         if self.mlp_mode == "f16split":
@@ -454,7 +464,9 @@ class DanboEngine(RenderEngine):
         flat_mode = (lazy and (fused or (S <= 256 and Sf <= 64)) and self.skip_flat_rays and self.flat_rays_ok
                      and act[0] == "relu")
         near, far = self.near_far(rays_o, rays_d, cyls, skts, 0.0, 1.0, chunk) if near_far is None else near_far
-        z = ops.coarse_samples(near, far, S)
+        # the culls of the listed rays alone: they make those rays' coarse depths themselves (z stays unwritten elsewhere)
+        listed_cull = flat_mode and self.cull_listed_rays and not part and skts.shape[0] == 1
+        z = torch.empty(rays_o.shape[0], S, device=rays_o.device, dtype=torch.float32) if listed_cull else ops.coarse_samples(near, far, S)
         # candidate bones of every ray over [near, far] (coarse and importance depths both lie inside): the two culls skip the
         # rays, and whole workgroups, that miss every volume -- most of a frame
         ray_mask = None if dense else ops.ray_bone_mask(rays_o, rays_d, skts, self.align, self.axis_scale, near, far,
@@ -470,7 +482,8 @@ class DanboEngine(RenderEngine):
         if ray_mask is not None:
             ray_mask = ray_mask[:3]
         raw, ex = self.forward_samples(rays_o, rays_d, skts, bones, cam_idx, z=z, dense=dense, volumes=vols, view=view,
-                                       fill=not lazy, ray_mask=ray_mask, count=counts[0:1], want_confd=bool(part))
+                                       fill=not lazy, ray_mask=ray_mask, count=counts[0:1], want_confd=bool(part),
+                                       listed=(flat, (near, far)) if listed_cull else None)
         if fused:
             out0, z_all, z_fine, order = ops.composite_importance(
                 raw, z, rays_d, Sf, B, bits=ex["valid_bits"] if lazy else None, raw_empty=view[1] if lazy else None,
@@ -481,7 +494,8 @@ class DanboEngine(RenderEngine):
             z_all, z_fine, order = ops.importance_samples(z, out0["weights"], Sf, flat=flat)
         raw_f, ex_f = self.forward_samples(rays_o, rays_d, skts, bones, cam_idx, z=z_fine, dense=dense,
                                            volumes=vols, view=view, fill=not lazy,
-                                           ray_mask=ray_mask, count=counts[1:2], want_confd=bool(part))
+                                           ray_mask=ray_mask, count=counts[1:2], want_confd=bool(part),
+                                           listed=(flat, None) if listed_cull else None)
         out = ops.composite_merged(raw, raw_f, order, z_all, rays_d, B, bits_a=ex["valid_bits"] if lazy else None,
                                    bits_b=ex_f["valid_bits"] if lazy else None, raw_empty=view[1] if lazy else None,
                                    want_raw=keep, flat=flat, act=act)

@@ -5,6 +5,7 @@
 // Host code only: it enqueues the kernels of the other translation units on `stream` in the order core/render_engine.py does,
 // carving every intermediate out of a caller-provided workspace; no allocation, no synchronisation.
 #include "common.hpp"
+#include "../../include/danbo_cull.h"
 
 using namespace danbo;
 
@@ -72,7 +73,10 @@ static int render_frame_impl(const DanboModel* m, const DanboRays* r, int S, int
                                       b.near, b.far, stream));
     if (m->use_volume_near_far)
         DANBO_TRY(danbo_near_far_boxes(r->rays_o, r->rays_d, r->skts, m->align, m->axis_scale, R, G, b.near, b.far, stream));
-    DANBO_TRY(danbo_coarse_samples(b.near, b.far, R, S, nullptr, b.z, stream));
+    // rays of constants and one pose: the culls below take the listed rays alone and make those rays' coarse depths themselves
+    // (danbo_bone_cull_rays; render()'s cull_listed_rays) -- b.z stays unwritten for every other ray, which nobody reads
+    const bool listed_cull = flat_rays && G == 1;
+    if (!listed_cull) DANBO_TRY(danbo_coarse_samples(b.near, b.far, R, S, nullptr, b.z, stream));
     // candidate bones of every ray over [near, far]: both culls below skip the rays (and workgroups) that miss every volume
     DANBO_TRY(danbo_ray_bone_mask(r->rays_o, r->rays_d, b.near, b.far, R, G, r->skts, m->align, m->axis_scale, b.ray_mask,
                                   flat_rays ? b.ray_flat : nullptr, stream));
@@ -97,7 +101,13 @@ static int render_frame_impl(const DanboModel* m, const DanboRays* r, int S, int
     }
     DANBO_TRY(view_consts(ray_list, ray_count));
     // one network pass over R x s samples at depths zz -> raw (rows outside every volume stay unwritten: bits == 0)
-    auto cull = [&](const float* zz, int s, uint32_t* bits, int32_t* count) -> int {
+    auto cull = [&](float* zz, int s, uint32_t* bits, int32_t* count) -> int {
+        if (listed_cull) {
+            const bool coarse = zz == b.z;      // the coarse pass makes its depths (into b.z), the importance pass reads b.z_fine
+            return danbo_bone_cull_rays(ray_list, ray_count, b.ray_mask, b.near, b.far, r->rays_o, r->rays_d, R, s, G, r->skts, m->align,
+                                        m->axis_scale, coarse ? b.near : nullptr, coarse ? b.far : nullptr, zz, 0, bits, b.list, count,
+                                        stream);
+        }
         DANBO_TRY(danbo_bone_cull(r->rays_o, r->rays_d, zz, nullptr, R, s, G, r->skts, m->align, m->axis_scale, b.ray_mask, b.near, b.far,
                                   nullptr, bits, b.list, count, stream));
         // (danbo_group_rows -- rows of the same bone set next to each other -- is not part of the chain any more: it costs what it

@@ -7,6 +7,7 @@
 // and |axis_scale| live in LDS for the whole workgroup; the 23 KB factorised volume of the
 // pose is staged in LDS by the gather kernel.
 #include "common.hpp"
+#include "cull_math.hpp"
 
 namespace danbo {
 
@@ -195,18 +196,7 @@ __global__ __launch_bounds__(256) void k_box_bounds(const float* __restrict__ ra
 // ======================================================================================
 // coarse samples
 // ======================================================================================
-__device__ __forceinline__ float coarse_sample(float n_, float f_, int s, int S, const float* __restrict__ t_rand, long m) {
-    float v = coarse_z(n_, f_, s, S);
-    if (t_rand) {  // stratified jitter (ray_utils.py:233-248)
-        const float zp = s > 0 ? coarse_z(n_, f_, s - 1, S) : v;
-        const float zn = s + 1 < S ? coarse_z(n_, f_, s + 1, S) : v;
-        const float lower = s > 0 ? mul_rn(0.5f, add_rn(v, zp)) : v;
-        const float upper = s + 1 < S ? mul_rn(0.5f, add_rn(zn, v)) : v;
-        v = add_rn(lower, mul_rn(sub_rn(upper, lower), t_rand[m]));
-    }
-    return v;
-}
-
+// (coarse_sample: sample_math.hpp)
 // S a multiple of 4: four depths of a ray per thread, one 16-byte store (the frame's 50 MB of depths are a pure write stream: 4-byte
 // stores reached 2.9 TB/s of the 6 a fill reaches)
 __global__ __launch_bounds__(256) void k_coarse_samples4(const float* __restrict__ nr, const float* __restrict__ fr,
@@ -263,41 +253,7 @@ __device__ __forceinline__ void load_point(const float* __restrict__ rays_o, con
 // ======================================================================================
 // K1a: transform + cull
 // ======================================================================================
-typedef float v2f __attribute__((ext_vector_type(2)));
-
-// ((m0*x + m1*y) + m2*z) + m3 for two points at once; every packed op rounds each half like the
-// scalar __fmul_rn / __fadd_rn chain of affine_unfused() (contraction disabled).
-// The matrix entries are BROADCAST over the pair.  Left to the compiler that is v_pk_mul_f32 x, m op_sel:[0,1] for the odd entries --
-// the low half from SRC1's high dword: the one operand selection that is wrong on gfx950 beside MFMA wavefronts (common.hpp,
-// DANBO_NO_PK_F32; without packed instructions this kernel takes 102 instead of 55 us).  Written out with the matrix pair as SRC0, whose
-// high-dword selection is exact (tools/probe/cview_probe.hip: 0 of 2.7e10), the products and sums are the same IEEE operations.
-template <int HI>
-__device__ __forceinline__ v2f pk_mul_bcast(v2f m, v2f x) {     // m[HI] * x
-    v2f d;
-    if (HI) asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1]" : "=v"(d) : "v"(m), "v"(x));
-    else asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[0,1]" : "=v"(d) : "v"(m), "v"(x));
-    return d;
-}
-__device__ __forceinline__ v2f pk_add(v2f a, v2f b) {
-    v2f d;
-    asm("v_pk_add_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
-__device__ __forceinline__ v2f pk_add_bcast_hi(v2f m, v2f a) {  // m[1] + a
-    v2f d;
-    asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1]" : "=v"(d) : "v"(m), "v"(a));
-    return d;
-}
-__device__ __forceinline__ void affine_pk(const float* M, v2f x, v2f y, v2f z, v2f* q) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float4 r = *reinterpret_cast<const float4*>(M + 4 * k);
-        const v2f m01 = {r.x, r.y}, m23 = {r.z, r.w};
-        v2f s = pk_add(pk_mul_bcast<0>(m01, x), pk_mul_bcast<1>(m01, y));
-        s = pk_add(s, pk_mul_bcast<0>(m23, z));
-        q[k] = pk_add_bcast_hi(m23, s);
-    }
-}
+// (v2f, affine_pk, mask_slack, in_volume_pk: cull_math.hpp -- shared with k_cull_rays.hip)
 
 // Conservative ray-level rejection shared by k_ray_bone_mask and the in-kernel prefilter of k_bone_cull: true when the
 // segment {o + t d : zl - pad <= t <= zh + pad} provably misses the slightly inflated box of the bone (margins far above the
@@ -463,7 +419,7 @@ __global__ __launch_bounds__(CULL_BLOCK) void k_bone_cull(const float* __restric
             if (base + k * CULL_BLOCK + threadIdx.x < M) {
                 const int r = r_first + ray_of(off0 + k * CULL_BLOCK + threadIdx.x);
                 const float lo = t_lo[r], hi = t_hi[r];
-                const float slack = 5e-5f * fmaxf(fabsf(lo), fabsf(hi));   // half of segment_misses_bone's pad
+                const float slack = mask_slack(lo, hi);
                 const bool inside = zreg[k] >= lo - slack && zreg[k] <= hi + slack;
                 pre[k] = inside ? ray_mask[r] : (1u << J) - 1u;
                 if (!inside && ray_flat != nullptr) ray_flat[r] = 0u;     // not a ray of constants after all (every writer stores 0)
@@ -560,18 +516,7 @@ __global__ __launch_bounds__(CULL_BLOCK) void k_bone_cull(const float* __restric
         if (__builtin_amdgcn_readfirstlane((int)__all(ga == gb))) {
             const v2f px = {pa[0], pb[0]}, py = {pa[1], pb[1]}, pz = {pa[2], pb[2]};
             const float* sk = s_skt + (ga - g0) * J * 16;
-            while (need) {
-                const int j = __builtin_ctz(need);
-                need &= need - 1u;
-                v2f l[3], t[3];
-                affine_pk(sk + 16 * j, px, py, pz, l);
-                affine_pk(s_align + 16 * j, l[0], l[1], l[2], t);
-                const float* sc = s_scale + 4 * j;
-                const bool ina = !(fabsf(t[0].x) > sc[0] || fabsf(t[1].x) > sc[1] || fabsf(t[2].x) > sc[2]);
-                const bool inb = !(fabsf(t[0].y) > sc[0] || fabsf(t[1].y) > sc[1] || fabsf(t[2].y) > sc[2]);
-                ba |= (ina ? 1u : 0u) << j;
-                bb |= (inb ? 1u : 0u) << j;
-            }
+            in_volume_pk(sk, s_align, s_scale, need, px, py, pz, ba, bb);
         } else {  // some pair of the wavefront straddles two poses (chunk boundaries only)
             const float* ska = s_skt + (ga - g0) * J * 16;
             const float* skb = s_skt + (gb - g0) * J * 16;

@@ -62,6 +62,20 @@ DANBO_HD float coarse_z(float nr, float fr, int s, int S) {
     return add_rn(mul_rn(nr, sub_rn(1.0f, t)), mul_rn(fr, t));
 }
 
+// coarse depth s of a ray: coarse_z, or (t_rand: one uniform per sample, read at [m]) the stratified jitter between the mid-points
+// to its neighbours (ray_utils.py:233-248).  One definition for k_coarse_samples* (k_sample.hip) and k_cull_rays (k_cull_rays.hip)
+DANBO_HD float coarse_sample(float n_, float f_, int s, int S, const float* __restrict__ t_rand, long m) {
+    float v = coarse_z(n_, f_, s, S);
+    if (t_rand) {  // stratified jitter (ray_utils.py:233-248)
+        const float zp = s > 0 ? coarse_z(n_, f_, s - 1, S) : v;
+        const float zn = s + 1 < S ? coarse_z(n_, f_, s + 1, S) : v;
+        const float lower = s > 0 ? mul_rn(0.5f, add_rn(v, zp)) : v;
+        const float upper = s + 1 < S ? mul_rn(0.5f, add_rn(zn, v)) : v;
+        v = add_rn(lower, mul_rn(sub_rn(upper, lower), t_rand[m]));
+    }
+    return v;
+}
+
 // pts = o + d*z (two roundings), core/raycasters.py:463
 DANBO_HD void sample_point(const float* o, const float* d, float z, float* p) {
     p[0] = add_rn(o[0], mul_rn(d[0], z));

@@ -69,7 +69,8 @@ extern "C" {
  * of the extracted mesh); danbo_part_colors_fwd, danbo_composite_colors_fwd (bone-assignment maps, --render_confd /
  * --render_entropy: declared in danbo_partmap.h beside this file, as the rasteriser's entries are in danbo_raster.h);
  * danbo_image_metrics_workspace_bytes, danbo_image_metrics (PSNR / SSIM sums of rendered frames on the device, --eval_device:
- * declared in danbo_metrics.h beside this file). */
+ * declared in danbo_metrics.h beside this file); danbo_bone_cull_rays (depths, in-volume words and rows of the listed rays of a
+ * frame only, which danbo_render_frame uses beside rays of constants: declared in danbo_cull.h beside this file). */
 #define DANBO_ABI_VERSION 9   /* what danbo_abi_version() of a library built from this header returns; the binding refuses another */
 int danbo_abi_version(void);
 int danbo_device_info(int* cu_count, int* lds_bytes, char* arch, int arch_len);
