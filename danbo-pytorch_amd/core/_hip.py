@@ -10,13 +10,11 @@ Every pointer, whatever it points to, is a `c_void_p` (`char*`: `c_char_p`): a p
 is skipped.  A new entry point needs its declaration in the header and its implementation, and is then callable as
 `call("danbo_x", ...)`; a wrapper in hip_ops is optional.
 
-The header is $DANBO_HIP_HEADER, else danbo_hip.h beside the library, else include/danbo_hip.h of the source tree.  The
-rasteriser's two entries stand in danbo_raster.h beside it and are bound the same way into RASTER_SIGNATURES / RASTER_RESTYPES /
-RASTER_C (tables of their own: SIGNATURES and C are the statement of danbo_hip.h alone); the two entries of the bone-assignment maps
-stand in danbo_partmap.h and are bound into PARTMAP_SIGNATURES / PARTMAP_RESTYPES, the two of the image metrics in
-danbo_metrics.h into METRICS_SIGNATURES / METRICS_RESTYPES, the listed-ray cull's in danbo_cull.h into CULL_SIGNATURES /
-CULL_RESTYPES.  `lib()` refuses
-a library whose danbo_abi_version() is not the header's DANBO_ABI_VERSION (a stale build).
+The header is $DANBO_HIP_HEADER, else danbo_hip.h beside the library, else include/danbo_hip.h of the source tree.  SIGNATURES,
+RESTYPES, STRUCTS and C are the statement of danbo_hip.h alone.  The entry points of a later feature stand in a header of their own
+beside it (a satellite), bound the same way and reached as `header("danbo_x.h").signatures / .restypes / .C / .path`: a satellite
+declares no struct, and no function or constant that an earlier header declares.  A new header is named in HEADERS, nowhere else.
+`lib()` refuses a library whose danbo_abi_version() is not the header's DANBO_ABI_VERSION (a stale build).
 
 The library is the only compute backend of this package: there is NO PyTorch/CPU fallback.  `lib()` raises if the shared object is
 missing, and every wrapper in hip_ops raises if a tensor is not a CUDA(HIP) tensor.
@@ -202,62 +200,46 @@ def _header_path():
                        + "; set DANBO_HIP_HEADER or put the header beside the library")
 
 
+HEADERS = ("danbo_hip.h", "danbo_raster.h", "danbo_partmap.h", "danbo_metrics.h", "danbo_cull.h")      # the core header, then the satellites
+
+
+def bind_headers(paths):
+    """-> one namespace (path, signatures, restypes, structs, C) per header file of `paths`, the core header first.  Every later one
+    is a satellite: HeaderError if it declares a struct, or a function or constant that a header before it declares."""
+    bound, owner = [], {}
+    for path in paths:
+        if not os.path.exists(path):
+            raise RuntimeError(f"{path} not found (the binding of its entry points is derived from it, it lies beside {HEADERS[0]})")
+        with open(path) as f:
+            functions, structs, constants = parse_header(f.read())
+        if bound:
+            if structs:
+                raise HeaderError(f"{path} declares struct {next(iter(structs))}: only {bound[0].path} declares structs")
+            for name in (*functions, *constants):
+                if name in owner:
+                    raise HeaderError(f"{path} declares {name}, which {owner[name]} declares")
+        owner.update(dict.fromkeys((*functions, *constants), path))
+        bound.append(SimpleNamespace(path=path, signatures={name: argtypes for name, (_, argtypes) in functions.items()},
+                                     restypes={name: restype for name, (restype, _) in functions.items()},
+                                     structs=structs, C=SimpleNamespace(**constants)))
+    return bound
+
+
 HEADER_PATH = _header_path()
-with open(HEADER_PATH) as _f:
-    _functions, _structs, _constants = parse_header(_f.read())
-SIGNATURES = {name: argtypes for name, (_, argtypes) in _functions.items()}
-RESTYPES = {name: restype for name, (restype, _) in _functions.items()}
+_BOUND = dict(zip(HEADERS, bind_headers([HEADER_PATH] + [os.path.join(os.path.dirname(HEADER_PATH), h) for h in HEADERS[1:]])))
+
+
+def header(name):
+    """what one of HEADERS declares: .path, .signatures {name: argtypes}, .restypes {name: restype}, .C (its constants)"""
+    return _BOUND[name]
+
+
+_core = header(HEADERS[0])
+SIGNATURES, RESTYPES, C = _core.signatures, _core.restypes, _core.C
 STRUCTS = {name: type(name, (ctypes.Structure,), {"_fields_": fields, "__doc__": f"struct {name} of include/danbo_hip.h"})
-           for name, fields in _structs.items()}
+           for name, fields in _core.structs.items()}
 globals().update(STRUCTS)              # _hip.DanboModel, _hip.DanboDwLayer, ...
-C = SimpleNamespace(**_constants)
 MAX_ROW_SPANS = C.DANBO_MAX_ROW_SPANS
-
-# ---- the rasteriser's entries (include/danbo_raster.h, beside danbo_hip.h): the same parser, tables of their own -- SIGNATURES and
-# C stay the statement of danbo_hip.h alone
-RASTER_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "danbo_raster.h")
-if not os.path.exists(RASTER_HEADER_PATH):
-    raise RuntimeError(f"{RASTER_HEADER_PATH} not found (the binding of the rasteriser is derived from it, it lies beside danbo_hip.h)")
-with open(RASTER_HEADER_PATH) as _f:
-    _r_functions, _r_structs, _r_constants = parse_header(_f.read())
-if _r_structs or set(_r_functions) & set(_functions) or set(_r_constants) & set(_constants):
-    raise HeaderError(f"{RASTER_HEADER_PATH} declares a struct, or a name danbo_hip.h declares")
-RASTER_SIGNATURES = {name: argtypes for name, (_, argtypes) in _r_functions.items()}
-RASTER_RESTYPES = {name: restype for name, (restype, _) in _r_functions.items()}
-RASTER_C = SimpleNamespace(**_r_constants)
-
-# ---- the bone-assignment maps' entries (include/danbo_partmap.h, beside danbo_hip.h), bound the same way
-PARTMAP_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "danbo_partmap.h")
-if not os.path.exists(PARTMAP_HEADER_PATH):
-    raise RuntimeError(f"{PARTMAP_HEADER_PATH} not found (the binding of the part maps is derived from it, it lies beside danbo_hip.h)")
-with open(PARTMAP_HEADER_PATH) as _f:
-    _p_functions, _p_structs, _p_constants = parse_header(_f.read())
-if _p_structs or _p_constants or set(_p_functions) & (set(_functions) | set(_r_functions)):
-    raise HeaderError(f"{PARTMAP_HEADER_PATH} declares a struct, a constant, or a name another header declares")
-PARTMAP_SIGNATURES = {name: argtypes for name, (_, argtypes) in _p_functions.items()}
-PARTMAP_RESTYPES = {name: restype for name, (restype, _) in _p_functions.items()}
-
-# ---- the image metrics' entries (include/danbo_metrics.h, beside danbo_hip.h), bound the same way
-METRICS_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "danbo_metrics.h")
-if not os.path.exists(METRICS_HEADER_PATH):
-    raise RuntimeError(f"{METRICS_HEADER_PATH} not found (the binding of the image metrics is derived from it, it lies beside danbo_hip.h)")
-with open(METRICS_HEADER_PATH) as _f:
-    _m_functions, _m_structs, _m_constants = parse_header(_f.read())
-if _m_structs or _m_constants or set(_m_functions) & (set(_functions) | set(_r_functions) | set(_p_functions)):
-    raise HeaderError(f"{METRICS_HEADER_PATH} declares a struct, a constant, or a name another header declares")
-METRICS_SIGNATURES = {name: argtypes for name, (_, argtypes) in _m_functions.items()}
-METRICS_RESTYPES = {name: restype for name, (restype, _) in _m_functions.items()}
-
-# ---- the listed-ray cull's entry (include/danbo_cull.h, beside danbo_hip.h), bound the same way
-CULL_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "danbo_cull.h")
-if not os.path.exists(CULL_HEADER_PATH):
-    raise RuntimeError(f"{CULL_HEADER_PATH} not found (the binding of the listed-ray cull is derived from it, it lies beside danbo_hip.h)")
-with open(CULL_HEADER_PATH) as _f:
-    _c_functions, _c_structs, _c_constants = parse_header(_f.read())
-if _c_structs or _c_constants or set(_c_functions) & (set(_functions) | set(_r_functions) | set(_p_functions) | set(_m_functions)):
-    raise HeaderError(f"{CULL_HEADER_PATH} declares a struct, a constant, or a name another header declares")
-CULL_SIGNATURES = {name: argtypes for name, (_, argtypes) in _c_functions.items()}
-CULL_RESTYPES = {name: restype for name, (restype, _) in _c_functions.items()}
 ANERF_MAX_D = C.DANBO_ANERF_MAX_D
 
 # ---- training step: the state_dict key of every slot of DanboTrainModel.p / .g (enum DanboTrainTensor; the names are Python's)
@@ -288,11 +270,11 @@ def lib():
                 f"{LIB_PATH} not found: build it with `make -C danbo-pytorch_amd/csrc` "
                 "(or __graft_entry__.build()).  There is no CPU / PyTorch fallback.")
         l = ctypes.CDLL(LIB_PATH)
-        for name, argtypes in {**SIGNATURES, **RASTER_SIGNATURES, **PARTMAP_SIGNATURES, **METRICS_SIGNATURES, **CULL_SIGNATURES}.items():
-            fn = getattr(l, name)
-            fn.argtypes = argtypes
-            fn.restype = (RESTYPES.get(name) or RASTER_RESTYPES.get(name) or PARTMAP_RESTYPES.get(name) or METRICS_RESTYPES.get(name)
-                          or CULL_RESTYPES[name])
+        for h in _BOUND.values():
+            for name, argtypes in h.signatures.items():
+                fn = getattr(l, name)
+                fn.argtypes = argtypes
+                fn.restype = h.restypes[name]
         if l.danbo_abi_version() != C.DANBO_ABI_VERSION:
             raise RuntimeError(f"{LIB_PATH} has ABI version {l.danbo_abi_version()}, {HEADER_PATH} declares {C.DANBO_ABI_VERSION}: "
                                "the library is stale, rebuild it with `make -C danbo-pytorch_amd/csrc`")

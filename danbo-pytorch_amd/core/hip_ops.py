@@ -960,8 +960,8 @@ def marching_cubes(sigma, iso, floor=float("-inf"), scale=1.0, offset=(0.0, 0.0,
 
 
 # -------------------------------------------------------------------------------------- mesh rasteriser
-RASTER_MODES = {"color": _hip.RASTER_C.DANBO_RASTER_COLOR, "normal": _hip.RASTER_C.DANBO_RASTER_NORMAL,
-                "flat": _hip.RASTER_C.DANBO_RASTER_FLAT}
+_rc = _hip.header("danbo_raster.h").C
+RASTER_MODES = {"color": _rc.DANBO_RASTER_COLOR, "normal": _rc.DANBO_RASTER_NORMAL, "flat": _rc.DANBO_RASTER_FLAT}
 
 
 def rasterize_mesh(verts, faces, attr=None, mode="normal", views=None, half_extent=0.6, size=(512, 512), background=(1.0, 1.0, 1.0),

@@ -11,7 +11,7 @@
  * has (tests/test_abi_binding.py counts them).  This header declares no struct and no constant.
  *
  * THIS FILE IS READ BY A PROGRAM, like danbo_hip.h and in the same subset of C (stated at the top of danbo_hip.h):
- * danbo-pytorch_amd/core/_hip.py parses it on import and derives CULL_SIGNATURES / CULL_RESTYPES from it.
+ * danbo-pytorch_amd/core/_hip.py parses it on import and binds it as header("danbo_cull.h").
  */
 #ifndef DANBO_CULL_H
 #define DANBO_CULL_H

@@ -12,8 +12,8 @@
  * (tests/test_abi_binding.py counts its entry points).  This header declares no struct and no constant.
  *
  * THIS FILE IS READ BY A PROGRAM, like danbo_hip.h and in the same subset of C (stated at the top of danbo_hip.h):
- * danbo-pytorch_amd/core/_hip.py parses it on import and derives METRICS_SIGNATURES / METRICS_RESTYPES from it;
- * tests/test_image_metrics_host.py checks what the parser derived against the host compiler's view of this file.
+ * danbo-pytorch_amd/core/_hip.py parses it on import and binds it as header("danbo_metrics.h");
+ * tests/test_abi_binding.py checks what the parser derived against the host compiler's view of this file.
  */
 #ifndef DANBO_METRICS_H
 #define DANBO_METRICS_H

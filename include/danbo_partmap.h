@@ -9,8 +9,8 @@
  * because danbo_hip.h is the pinned statement of the render and training path (tests/test_abi_binding.py counts its entry points).
  *
  * THIS FILE IS READ BY A PROGRAM, like danbo_hip.h and in the same subset of C (stated at the top of danbo_hip.h):
- * danbo-pytorch_amd/core/_hip.py parses it on import and derives PARTMAP_SIGNATURES / PARTMAP_RESTYPES from it;
- * tests/test_part_maps_host.py checks what the parser derived against the host compiler's view of this file.
+ * danbo-pytorch_amd/core/_hip.py parses it on import and binds it as header("danbo_partmap.h");
+ * tests/test_abi_binding.py checks what the parser derived against the host compiler's view of this file.
  */
 #ifndef DANBO_PARTMAP_H
 #define DANBO_PARTMAP_H

@@ -8,8 +8,8 @@
  * of the render and training path (tests/test_abi_binding.py counts its entry points and constants).
  *
  * THIS FILE IS READ BY A PROGRAM, like danbo_hip.h and in the same subset of C (stated at the top of danbo_hip.h):
- * danbo-pytorch_amd/core/_hip.py parses it on import and derives RASTER_SIGNATURES / RASTER_RESTYPES / RASTER_C from it;
- * tests/test_raster_host.py checks what the parser derived against the host compiler's view of this file.
+ * danbo-pytorch_amd/core/_hip.py parses it on import and binds it as header("danbo_raster.h");
+ * tests/test_abi_binding.py checks what the parser derived against the host compiler's view of this file.
  */
 #ifndef DANBO_RASTER_H
 #define DANBO_RASTER_H

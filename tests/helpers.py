@@ -1,10 +1,37 @@
 """Shared helpers for the test-suite: golden fixtures, synthetic inputs, oracle construction."""
+import ctypes
 import os
 
 import numpy as np
+import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+
+DEV = "cuda:0"
+EINVAL = -22        # DANBO_EINVAL
+# an address no check ever follows (16-byte aligned, not null): for calls that return before a launch
+_BUF = (ctypes.c_float * 64)()
+ADDR = (ctypes.addressof(_BUF) + 15) & ~15
+
+
+def hip_lib():
+    """the loaded, bound libdanbo_hip.so"""
+    from core import _hip
+    return _hip.lib()
+
+
+def T(x, dtype=torch.float32):
+    return torch.tensor(np.ascontiguousarray(x), dtype=dtype, device=DEV)
+
+
+def N(t):
+    return t.detach().cpu().numpy()
+
+
+def same_bits(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
 def golden(name):

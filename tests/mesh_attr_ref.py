@@ -2,13 +2,11 @@
 mesh_normals_host of csrc/mesh_math.hpp built with g++ at test time, an independent float64 numpy evaluation of the definition it
 is checked against, the grids of the definition's edges."""
 import ctypes
-import functools
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+import hostlib
 import mesh_ref as m
 
 F32 = np.float32
@@ -27,15 +25,9 @@ int ref_mesh_normals(const float* sigma, int nx, int ny, int nz, long sx, long s
 '''
 
 
-@functools.lru_cache(maxsize=None)
 def host_lib():
     """g++ -std=c++17 -ffp-contract=off build of mesh_normals_host (as mesh_ref.host_lib builds the extractor)"""
-    d = tempfile.mkdtemp(prefix="danbo_mesh_attr_ref_")
-    src, so = os.path.join(d, "mesh_attr_ref.cpp"), os.path.join(d, "libmesh_attr_ref.so")
-    with open(src, "w") as f:
-        f.write(_WRAPPER % os.path.join(m.CSRC, "mesh_math.hpp"))
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, src])
-    lib = ctypes.CDLL(so)
+    lib = hostlib.build("mesh_attr_ref", _WRAPPER % os.path.join(m.CSRC, "mesh_math.hpp"))
     c = ctypes
     grid = [c.c_void_p, c.c_int, c.c_int, c.c_int, c.c_long, c.c_long, c.c_float, c.c_float, c.c_void_p]
     lib.ref_mesh_count.argtypes = grid + [c.c_void_p]

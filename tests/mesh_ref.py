@@ -2,14 +2,12 @@
 csrc/mesh_math.hpp built with g++ at test time, the numpy predictions it is checked against, the test grids."""
 import collections
 import ctypes
-import functools
 import importlib.util
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+import hostlib
 from helpers import ROOT
 
 F32 = np.float32
@@ -32,15 +30,9 @@ unsigned long long ref_mc_case(int m) { return MC_CASE[m & 255]; }
 '''
 
 
-@functools.lru_cache(maxsize=None)
 def host_lib():
     """g++ -std=c++17 -ffp-contract=off build of the serial extractor (csrc/mesh_math.hpp + csrc/mc_table.inc)"""
-    d = tempfile.mkdtemp(prefix="danbo_mesh_ref_")
-    src, so = os.path.join(d, "mesh_ref.cpp"), os.path.join(d, "libmesh_ref.so")
-    with open(src, "w") as f:
-        f.write(_WRAPPER % os.path.join(CSRC, "mesh_math.hpp"))
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, src])
-    lib = ctypes.CDLL(so)
+    lib = hostlib.build("mesh_ref", _WRAPPER % os.path.join(CSRC, "mesh_math.hpp"))
     c = ctypes
     lib.ref_mesh_count.argtypes = [c.c_void_p, c.c_int, c.c_int, c.c_int, c.c_long, c.c_long, c.c_float, c.c_float, c.c_void_p, c.c_void_p]
     lib.ref_mesh_extract.argtypes = ([c.c_void_p, c.c_int, c.c_int, c.c_int, c.c_long, c.c_long, c.c_float, c.c_float, c.c_void_p]

@@ -2,13 +2,11 @@
 of csrc/metrics_math.hpp built with g++ at test time, a float64 numpy evaluation of the crop-then-zero-pad SSIM and the squared
 error, and the textured test frames."""
 import ctypes
-import functools
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+import hostlib
 import mesh_ref
 from helpers import ROOT
 
@@ -33,15 +31,9 @@ int ref_tile_w(void) { return METRICS_TILE_W; }
 '''
 
 
-@functools.lru_cache(maxsize=None)
 def host_lib():
     """g++ -O2 -std=c++17 -ffp-contract=off build of the serial restatement (csrc/metrics_math.hpp)"""
-    d = tempfile.mkdtemp(prefix="danbo_metrics_ref_")
-    src, so = os.path.join(d, "metrics_ref.cpp"), os.path.join(d, "libmetrics_ref.so")
-    with open(src, "w") as f:
-        f.write(_WRAPPER % os.path.join(CSRC, "metrics_math.hpp"))
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, src])
-    lib = ctypes.CDLL(so)
+    lib = hostlib.build("metrics_ref", _WRAPPER % os.path.join(CSRC, "metrics_math.hpp"))
     c = ctypes
     lib.ref_metrics_workspace_bytes.argtypes = [c.c_int] * 3
     lib.ref_metrics_workspace_bytes.restype = c.c_size_t

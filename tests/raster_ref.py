@@ -4,11 +4,10 @@ colour), the test scenes."""
 import ctypes
 import functools
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+import hostlib
 import mesh_ref
 from helpers import ROOT
 
@@ -45,15 +44,9 @@ unsigned long long ref_raster_key(float depth, int tri) { return raster_key(dept
 '''
 
 
-@functools.lru_cache(maxsize=None)
 def host_lib():
     """g++ -O2 -std=c++17 -ffp-contract=off build of the serial rasteriser (csrc/raster_math.hpp)"""
-    d = tempfile.mkdtemp(prefix="danbo_raster_ref_")
-    src, so = os.path.join(d, "raster_ref.cpp"), os.path.join(d, "libraster_ref.so")
-    with open(src, "w") as f:
-        f.write(_WRAPPER % os.path.join(CSRC, "raster_math.hpp"))
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, src])
-    lib = ctypes.CDLL(so)
+    lib = hostlib.build("raster_ref", _WRAPPER % os.path.join(CSRC, "raster_math.hpp"))
     c = ctypes
     lib.ref_raster_workspace_bytes.argtypes = [c.c_int] * 3
     lib.ref_raster_workspace_bytes.restype = c.c_size_t

@@ -1,7 +1,8 @@
 """The ctypes binding that core/_hip.py derives from include/danbo_hip.h, checked against the host compiler's reading of the same
 header: struct layouts, constants and the type class of every parameter and result.  The compiler is the referee -- the lists of
 functions and structs come from this file's own regexes, never from the parser, so a declaration the parser dropped fails here.
-No GPU: the library is not even loaded, except by the stale-library case."""
+The same referee reads every satellite header of _hip.HEADERS (one row of SATELLITES each).  No GPU: the library is loaded (by the
+satellites' test and the stale-library case), nothing is launched."""
 import ctypes
 import os
 import re
@@ -9,6 +10,7 @@ import subprocess
 
 import pytest
 
+import raster_ref as rr
 from core import _hip
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -16,7 +18,14 @@ INCLUDE = os.path.join(ROOT, "include")
 with open(os.path.join(INCLUDE, "danbo_hip.h")) as _f:
     HEADER = _f.read()
 BARE = re.sub(r"/\*.*?\*/", " ", HEADER, flags=re.S)
-FUNCTIONS = sorted(set(re.findall(r"^(?:int|size_t|long)\s+(danbo_\w+)\s*\(", HEADER, flags=re.M)))
+
+
+def declared_functions(text):
+    """the entry points a header declares, by this file's own reading of its text"""
+    return sorted(set(re.findall(r"^(?:int|size_t|long)\s+(danbo_\w+)\s*\(", text, flags=re.M)))
+
+
+FUNCTIONS = declared_functions(HEADER)
 STRUCT_BODIES = dict(re.findall(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}", BARE, flags=re.S))
 
 
@@ -29,15 +38,18 @@ def compile_and_run(tmp_path_factory, compiler, name, source):
 
 
 # ------------------------------------------------------------------ layouts and constants
+# CONST(NAME) prints `const NAME kind value` as the C compiler reads the constant (kind: i integer, f float, d double)
+C_CONST = ['#include <stdio.h>', '#include <stddef.h>',
+           '#define KIND(x) _Generic((x), float: "f", double: "d", int: "i", long: "i", long long: "i", unsigned: "i", '
+           'unsigned long: "i", unsigned long long: "i")',
+           '#define CONST(x) printf("const %s %s ", #x, KIND(x)); if (KIND(x)[0] == \'i\') printf("%lld\\n", (long long)(x)); '
+           'else printf("%.17g\\n", (double)(x));']
+
+
 @pytest.fixture(scope="module")
 def c_view(tmp_path_factory):
     """what the host C compiler makes of the header: {("sizeof", S): n, ("field", S, f): (offset, size), ("const", NAME): (kind, text)}"""
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "danbo_hip.h"',
-             '#define KIND(x) _Generic((x), float: "f", double: "d", int: "i", long: "i", long long: "i", unsigned: "i", '
-             'unsigned long: "i", unsigned long long: "i")',
-             '#define CONST(x) printf("const %s %s ", #x, KIND(x)); if (KIND(x)[0] == \'i\') printf("%lld\\n", (long long)(x)); '
-             'else printf("%.17g\\n", (double)(x));',
-             'int main(void) {']
+    lines = ['#include "danbo_hip.h"'] + C_CONST + ['int main(void) {']
     for s, cls in _hip.STRUCTS.items():
         lines.append(f'printf("sizeof {s} %zu\\n", sizeof({s}));')
         lines += [f'printf("field {s} {f} %zu %zu\\n", offsetof({s}, {f}), sizeof((({s}*)0)->{f}));' for f, _ in cls._fields_]
@@ -97,9 +109,18 @@ for _l, _t in _C_TYPES.items():
     _LETTER.setdefault(_t, _l)
 
 
-def test_signatures_equal_the_host_compilers(tmp_path_factory):
-    assert len(FUNCTIONS) == 104
-    src = ['#include <cstdio>', '#include <cstddef>', '#include <type_traits>', '#include "danbo_hip.h"',
+def bound_letters(h, name):
+    return _LETTER[h.restypes[name]] + ":" + "".join(_LETTER[t] for t in h.signatures[name])
+
+
+def same_class(seen):
+    """the compiler's letters with every C type replaced by the letter of its ctypes class"""
+    return "".join(_LETTER[_C_TYPES[ch]] if ch in _C_TYPES else ch for ch in seen)
+
+
+def compiled_signatures(tmp_path_factory, includes, names):
+    """{name: "r:args"}: the type class of the result and of every parameter of each function, as a C++ compiler reads `includes`"""
+    src = ['#include <cstdio>', '#include <cstddef>', '#include <type_traits>'] + [f'#include "{h}"' for h in includes] + [
            'template <class T> constexpr char letter() {',
            '    if constexpr (std::is_pointer_v<T>) return \'P\';',
            '    else if constexpr (std::is_same_v<T, int>) return \'i\';',
@@ -116,13 +137,113 @@ def test_signatures_equal_the_host_compilers(tmp_path_factory):
            '        std::printf("%s %c:%s\\n", name, letter<R>(), args);',
            '    }',
            '};',
-           'int main() {'] + [f'    Sig<decltype({n})>::print("{n}");' for n in FUNCTIONS] + ['}']
-    seen = dict(line.split() for line in compile_and_run(tmp_path_factory, ["g++", "-std=c++17"], "sig.cpp", "\n".join(src)))
+           'int main() {'] + [f'    Sig<decltype({n})>::print("{n}");' for n in names] + ['}']
+    return dict(line.split() for line in compile_and_run(tmp_path_factory, ["g++", "-std=c++17"], "sig.cpp", "\n".join(src)))
+
+
+def test_signatures_equal_the_host_compilers(tmp_path_factory):
+    assert len(FUNCTIONS) == 104
+    seen = compiled_signatures(tmp_path_factory, ["danbo_hip.h"], FUNCTIONS)
     assert set(seen) == set(FUNCTIONS) == set(_hip.SIGNATURES) == set(_hip.RESTYPES)
     for name in FUNCTIONS:
         assert "?" not in seen[name], (name, seen[name])
-        bound = _LETTER[_hip.RESTYPES[name]] + ":" + "".join(_LETTER[t] for t in _hip.SIGNATURES[name])
-        assert "".join(_LETTER[_C_TYPES[ch]] if ch in _C_TYPES else ch for ch in seen[name]) == bound, (name, seen[name], bound)
+        bound = bound_letters(_hip.header("danbo_hip.h"), name)
+        assert same_class(seen[name]) == bound, (name, seen[name], bound)
+
+
+# ------------------------------------------------------------------ the satellite headers
+# one row per header of _hip.HEADERS[1:]: its entry points as "result:parameters" letters (above), its constants, and the words by
+# which the ABI history of danbo_hip.h names its entries
+SATELLITES = {
+    "danbo_raster.h": dict(functions={"danbo_raster_workspace_bytes": "z:iii", "danbo_raster_mesh": "i:PiPiPiPifiiPPPPPP"},
+                           constants={"DANBO_RASTER_COLOR": rr.COLOR, "DANBO_RASTER_NORMAL": rr.NORMAL, "DANBO_RASTER_FLAT": rr.FLAT},
+                           history="the rasteriser's entries are in danbo_raster.h"),
+    "danbo_partmap.h": dict(functions={"danbo_part_colors_fwd": "i:PPPPiiiPPP", "danbo_composite_colors_fwd": "i:PPPPPPiiiPPPP"},
+                            constants={}, history="danbo_part_colors_fwd, danbo_composite_colors_fwd"),
+    "danbo_metrics.h": dict(functions={"danbo_image_metrics_workspace_bytes": "z:iii", "danbo_image_metrics": "i:PPPPPiiiPiPPPP"},
+                            constants={}, history="danbo_image_metrics_workspace_bytes, danbo_image_metrics"),
+    "danbo_cull.h": dict(functions={"danbo_bone_cull_rays": "i:PPPPPPPiiiPPPPPPiPPPP"},      # 21 parameters, the stream last
+                         constants={}, history="danbo_bone_cull_rays"),
+}
+
+
+def test_every_satellite_has_its_row():
+    core = _hip.header("danbo_hip.h")
+    assert _hip.HEADERS[0] == "danbo_hip.h" and core.path == _hip.HEADER_PATH
+    assert core.signatures is _hip.SIGNATURES and core.restypes is _hip.RESTYPES and core.C is _hip.C
+    assert set(_hip.HEADERS[1:]) == set(SATELLITES) and len(set(_hip.HEADERS)) == len(_hip.HEADERS)
+
+
+@pytest.mark.parametrize("name", _hip.HEADERS[1:])
+def test_satellite_header_as_the_host_compilers_read_it(name, tmp_path_factory):
+    """a header beside danbo_hip.h: what it declares (by this file's regex, never the parser's tables) is what is bound, what the
+    row pins and what the C and the C++ compiler read; the library exports every entry and lib() has set its types"""
+    h, row = _hip.header(name), SATELLITES[name]
+    assert os.path.basename(h.path) == name and os.path.dirname(h.path) == os.path.dirname(_hip.HEADER_PATH)
+    with open(h.path) as f:
+        text = f.read()
+    functions = declared_functions(text)
+    assert set(functions) == set(row["functions"]) == set(h.signatures) == set(h.restypes)
+    parsed, structs, constants = _hip.parse_header(text)
+    assert not structs and constants == row["constants"] == vars(h.C) and set(parsed) == set(functions)
+    for other in _hip.HEADERS:                               # its names are its own
+        o = _hip.header(other)
+        if other != name:
+            assert not set(h.signatures) & set(o.signatures) and not set(vars(h.C)) & set(vars(o.C)), other
+    assert row["history"] in HEADER
+    # the C compiler: the header alone, then beside danbo_hip.h, then a second time; every constant read back
+    src = [f'#include "{name}"', '#include "danbo_hip.h"', f'#include "{name}"'] + C_CONST + ['int main(void) {']
+    src += [f"CONST({c})" for c in row["constants"]] + ["return 0; }"]
+    lines = compile_and_run(tmp_path_factory, ["cc", "-std=c11", "-Wall", "-Werror"], "const.c", "\n".join(src))
+    assert {w[1]: (w[2], int(w[3])) for w in map(str.split, lines)} == {c: ("i", v) for c, v in row["constants"].items()}
+    assert all(type(v) is int for v in vars(h.C).values())
+    # the C++ compiler: the type class of every parameter and result
+    seen = compiled_signatures(tmp_path_factory, [name, "danbo_hip.h", name], functions)
+    assert set(seen) == set(functions)
+    lib = _hip.lib()
+    raw = ctypes.CDLL(lib._name)
+    for fn, pinned in row["functions"].items():
+        assert "?" not in seen[fn], (fn, seen[fn])
+        assert seen[fn] == same_class(seen[fn]) == bound_letters(h, fn) == pinned, (fn, seen[fn], bound_letters(h, fn), pinned)
+        restype, _, args = pinned.partition(":")
+        assert h.restypes[fn] is _C_TYPES[restype] and h.signatures[fn] == [_C_TYPES[ch] for ch in args], fn
+        assert hasattr(raw, fn), fn
+        assert getattr(lib, fn).restype is h.restypes[fn] and getattr(lib, fn).argtypes == h.signatures[fn], fn
+    assert lib.danbo_abi_version() == _hip.C.DANBO_ABI_VERSION == 9
+
+
+CORE = "#define DANBO_N 8\nint danbo_f(int n);\ntypedef struct DanboS { int n; } DanboS;\n"
+FIRST = "#define DANBO_FIRST 1\nsize_t danbo_first(const float* s);\n"
+
+
+def bind(tmp_path, **texts):
+    for name, text in texts.items():
+        if text is not None:
+            (tmp_path / f"{name}.h").write_text(text)
+    return _hip.bind_headers([str(tmp_path / f"{name}.h") for name in texts])
+
+
+def test_bind_headers_binds_each_header_into_tables_of_its_own(tmp_path):
+    core, first, probe = bind(tmp_path, core=CORE, first=FIRST, danbo_probe="int danbo_probe(float x, void* stream);\n")
+    assert core.signatures == {"danbo_f": [ctypes.c_int]} and vars(core.C) == {"DANBO_N": 8} and list(core.structs) == ["DanboS"]
+    assert first.signatures == {"danbo_first": [ctypes.c_void_p]} and first.restypes == {"danbo_first": ctypes.c_size_t}
+    assert vars(first.C) == {"DANBO_FIRST": 1} and not first.structs
+    assert probe.signatures == {"danbo_probe": [ctypes.c_float, ctypes.c_void_p]} and probe.restypes == {"danbo_probe": ctypes.c_int}
+    assert vars(probe.C) == {} and probe.path == str(tmp_path / "danbo_probe.h")
+
+
+@pytest.mark.parametrize("text, error, quoted", [
+    ("typedef struct DanboT { int a; } DanboT;", _hip.HeaderError, "struct DanboT"),      # a satellite with a struct
+    ("int danbo_f(float x);", _hip.HeaderError, "danbo_f"),                               # a function of the core header
+    ("#define DANBO_N 9", _hip.HeaderError, "DANBO_N"),                                   # a constant of the core header
+    ("enum E { DANBO_FIRST };", _hip.HeaderError, "DANBO_FIRST"),                         # a constant of an earlier satellite
+    ("int danbo_first(void);", _hip.HeaderError, "danbo_first"),                          # a function of an earlier satellite
+    (None, RuntimeError, "not found"),                                                    # a missing file
+], ids=["struct", "core_function", "core_constant", "satellite_constant", "satellite_function", "missing_file"])
+def test_bind_headers_refuses_a_satellite_that_breaks_the_rule(tmp_path, text, error, quoted):
+    with pytest.raises(error) as e:
+        bind(tmp_path, core=CORE, first=FIRST, danbo_probe=text)
+    assert "danbo_probe.h" in str(e.value) and quoted in str(e.value), str(e.value)
 
 
 # ------------------------------------------------------------------ the parser on small headers

@@ -7,18 +7,10 @@ import pytest
 import torch
 
 import danbo_oracle as o
-from helpers import ROOT, golden, oracle_for, max_err, rel_err, raw_err, raw_rel_unfloored
+from helpers import ROOT, golden, oracle_for, max_err, rel_err, raw_err, raw_rel_unfloored, T, N
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def T(x, dtype=torch.float32):
-    return torch.tensor(np.ascontiguousarray(x), dtype=dtype, device=DEV)
-
-
-def N(t):
-    return t.detach().cpu().numpy()
 
 
 @pytest.fixture(scope="module")

@@ -9,18 +9,10 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import ROOT, golden
+from helpers import ROOT, golden, T, N
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def T(x, dtype=torch.float32):
-    return torch.tensor(np.ascontiguousarray(x), dtype=dtype, device=DEV)
-
-
-def N(t):
-    return t.detach().cpu().numpy()
 
 
 def build(g, extra=(), perturb="0", noise="0"):

@@ -15,7 +15,7 @@ import pytest
 import torch
 
 import danbo_oracle as o
-from helpers import ROOT, assignment_f64, blend_f64, synthetic
+from helpers import ROOT, assignment_f64, blend_f64, synthetic, T, N
 
 pytestmark = pytest.mark.gpu
 
@@ -23,14 +23,6 @@ DEV = "cuda:0"
 J = 24
 H_BOUND, LOGIT_BOUND = 5e-6, 2e-5
 SENTINEL = 12345.0
-
-
-def T(x, dtype=torch.float32):
-    return torch.tensor(np.ascontiguousarray(x), dtype=dtype, device=DEV)
-
-
-def N(t):
-    return t.detach().cpu().numpy()
 
 
 def _ops():

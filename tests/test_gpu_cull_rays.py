@@ -4,24 +4,16 @@ danbo_bone_cull on the same inputs.  Everything here is bit for bit: the per-sam
 
 Scene: core.utils.synthetic.make_scene at 32 x 32 rays (R = 1024), one pose, the danbo_base synthetic weights; (S, Sf) = (48, 16),
 (10, 4) (S no multiple of 4) and (96, 32) (the unfused composites)."""
-import ctypes
-import os
-import subprocess
-
-import numpy as np
 import pytest
 import torch
 
 import isa
+from helpers import ADDR as P, T     # P: an address no check follows -- the calls that take it return before any launch
 
 DEV = "cuda:0"
 SHAPES = [(48, 16), (10, 4), (96, 32)]
 CANARY_F, CANARY_I = -777.25, -12345
 KEYS = ("rgb_map", "disp_map", "acc_map", "alpha", "T_i", "rgb0", "disp0", "acc0", "alpha0")
-
-
-def T(x, dtype=torch.float32):
-    return torch.tensor(np.ascontiguousarray(x), dtype=dtype, device=DEV)
 
 
 @pytest.fixture(scope="module")
@@ -205,39 +197,6 @@ def test_listed_cull_does_not_spill():
         assert int(meta.group(1)) == 0, (k, meta.group(1))
         body = "\n".join(isa.kernel_body(text, r"_ZN5danbo\S*" + k + r"\S*"))
         assert "scratch_" not in body, k
-
-
-def test_cull_header_binding_as_the_host_compilers_read_it(tmp_path):
-    """include/danbo_cull.h: a C compiler accepts it alone and beside danbo_hip.h, and a C++ compiler states the type class of every
-    parameter of its entry as the parser bound it (the referee of tests/test_abi_binding.py, applied to this header); the library
-    exports the entry and danbo_hip.h -- whose entry points stay as they are -- names it in its ABI history"""
-    from core import _hip
-    assert set(_hip.CULL_SIGNATURES) == {"danbo_bone_cull_rays"} and not set(_hip.CULL_SIGNATURES) & set(_hip.SIGNATURES)
-    inc = os.path.dirname(_hip.CULL_HEADER_PATH)
-    assert inc == os.path.dirname(_hip.HEADER_PATH)
-    with open(_hip.HEADER_PATH) as f:
-        assert "danbo_bone_cull_rays" in f.read()
-    (tmp_path / "c.c").write_text('#include "danbo_cull.h"\n#include "danbo_hip.h"\n#include "danbo_cull.h"\nint main(void) { return 0; }\n')
-    subprocess.check_call(["cc", "-std=c11", "-Wall", "-Werror", "-I", inc, "-o", str(tmp_path / "c"), str(tmp_path / "c.c")])
-    letters = {ctypes.c_void_p: "P", ctypes.c_int: "i", ctypes.c_float: "f"}
-    cpp = ['#include <cstdio>', '#include <type_traits>', '#include "danbo_cull.h"',
-           'template <class T> constexpr char letter() {',
-           "    if constexpr (std::is_pointer_v<T>) return 'P'; else if constexpr (std::is_same_v<T, int>) return 'i';",
-           "    else if constexpr (std::is_same_v<T, float>) return 'f'; else return '?';", '}',
-           'template <class F> struct Sig;',
-           'template <class R, class... A> struct Sig<R(A...)> {',
-           '    static void print(const char* name) { const char args[] = {letter<A>()..., 0}; std::printf("%s %c:%s\\n", name, letter<R>(), args); }',
-           '};', 'int main() { Sig<decltype(danbo_bone_cull_rays)>::print("danbo_bone_cull_rays"); }']
-    (tmp_path / "s.cpp").write_text("\n".join(cpp))
-    subprocess.check_call(["g++", "-std=c++17", "-I", inc, "-o", str(tmp_path / "s"), str(tmp_path / "s.cpp")])
-    name, sig = subprocess.check_output([str(tmp_path / "s")], text=True).split()
-    bound = letters[_hip.CULL_RESTYPES[name]] + ":" + "".join(letters[t] for t in _hip.CULL_SIGNATURES[name])
-    assert sig == bound == "i:PPPPPPPiiiPPPPPPiPPPP", (sig, bound)      # 21 parameters, the stream last
-    fn = _hip.lib().danbo_bone_cull_rays
-    assert fn.argtypes == _hip.CULL_SIGNATURES[name] and _hip.lib().danbo_abi_version() == 9
-
-
-P = 4096        # a non-null address: the calls below return before anything is launched or read
 
 
 @pytest.mark.parametrize("kw", [dict(G=2), dict(G=0), dict(R=0), dict(S=0), dict(S=16385), dict(R=1 << 20, S=4096), dict(rpw=-1),

@@ -8,14 +8,10 @@ import pytest
 import torch
 
 import danbo_oracle as o
-from helpers import ROOT, golden, max_err
+from helpers import ROOT, golden, max_err, T
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def T(x, dtype=torch.float32):
-    return torch.tensor(np.ascontiguousarray(x), dtype=dtype, device=DEV)
 
 
 def _surreal_caster(g):

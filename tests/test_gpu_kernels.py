@@ -10,19 +10,11 @@ import pytest
 import torch
 
 import danbo_oracle as o
-from helpers import golden, oracle_for, max_err, rel_err, raw_err
+from helpers import golden, oracle_for, max_err, rel_err, raw_err, T, N
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-
-
-def T(x, dtype=torch.float32):
-    return torch.tensor(np.ascontiguousarray(x), dtype=dtype, device=DEV)
-
-
-def N(t):
-    return t.detach().cpu().numpy()
 
 
 @pytest.fixture(scope="module")

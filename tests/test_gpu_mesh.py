@@ -9,15 +9,11 @@ import pytest
 import torch
 
 import mesh_ref as m
-from helpers import ROOT, golden
+from helpers import ROOT, golden, T, same_bits
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 F32 = np.float32
-
-
-def T(x, dtype=torch.float32):
-    return torch.tensor(np.ascontiguousarray(x), dtype=dtype, device=DEV)
 
 
 def gpu_extract(sigma_t, iso, floor=-np.inf, scale=1.0, offset=(0., 0., 0.)):
@@ -26,10 +22,6 @@ def gpu_extract(sigma_t, iso, floor=-np.inf, scale=1.0, offset=(0., 0., 0.)):
     assert v.dtype == torch.float32 and f.dtype == torch.int32 and v.is_cuda and f.is_cuda
     assert v.dim() == 2 and v.shape[1] == 3 and f.dim() == 2 and f.shape[1] == 3
     return v.cpu().numpy(), f.cpu().numpy()
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
 def grids():

@@ -12,25 +12,13 @@ import torch
 import danbo_oracle as o
 import mesh_attr_ref as a
 import mesh_ref as m
-from helpers import ROOT, golden, oracle_for
+from helpers import ROOT, golden, oracle_for, T, N, same_bits
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 F32 = np.float32
 U = 2.0 ** -24
 COLOR_BOUND = 2.5e-5 + U          # the project's 1e-4 on a raw logit through the sigmoid's slope of 1/4, and the sigmoid's own rounding
-
-
-def T(x, dtype=torch.float32):
-    return torch.tensor(np.ascontiguousarray(x), dtype=dtype, device=DEV)
-
-
-def N(t):
-    return t.detach().cpu().numpy()
-
-
-def same_bits(x, y):
-    return x.shape == y.shape and x.dtype == y.dtype and x.tobytes() == y.tobytes()
 
 
 # ----------------------------------------------------------------------------- 8. kernel = serial restatement, bit for bit

@@ -7,18 +7,10 @@ import pytest
 import torch
 
 import danbo_oracle as o
-from helpers import ROOT, golden, max_err, rel_err, raw_err
+from helpers import ROOT, golden, max_err, rel_err, raw_err, T, N
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def T(x, dtype=torch.float32):
-    return torch.tensor(np.ascontiguousarray(x), dtype=dtype, device=DEV)
-
-
-def N(t):
-    return t.detach().cpu().numpy()
 
 
 def build(cfg_file, g, rest_scale=0.48):

@@ -17,7 +17,7 @@ import pytest
 import torch
 
 import danbo_oracle as o
-from helpers import ROOT, golden
+from helpers import ROOT, golden, T
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -27,10 +27,6 @@ ENTROPY_TOL = 1e-5
 COMPOSITE_TOL = 2e-5
 S_E2E, SF_E2E = 12, 6
 E2E_SUM_TOL = (S_E2E + SF_E2E) * 2.0 ** -24 * 1.01          # N 2^-24 sum |terms|, sum w <= 1 up to its own rounding
-
-
-def T(x, dtype=torch.float32):
-    return torch.tensor(np.ascontiguousarray(x), dtype=dtype, device=DEV)
 
 
 def clone(d):

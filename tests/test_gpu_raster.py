@@ -9,21 +9,13 @@ import pytest
 import torch
 
 import raster_ref as rr
-from helpers import ROOT, golden
+from helpers import ROOT, golden, T, same_bits
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 F32 = np.float32
 GUARD = rr.GUARD
 SIZES = ((1, 1), (5, 7), (64, 64), (80, 96))          # 80 x 96: W no multiple of 64, more than one wavefront per row
-
-
-def T(x, dtype=torch.float32):
-    return torch.tensor(np.ascontiguousarray(x), dtype=dtype, device=DEV)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
 def gpu_raster(verts, faces, attr, mode, views, hx, H, W, background=(1., 1., 1.), want=("rgb", "depth", "tri_id")):

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 import danbo_oracle as o
-from helpers import ROOT, max_err, raw_err
+from helpers import ROOT, max_err, raw_err, N
 from test_softplus_oracle import check_composite, composite, regime_rays, regime_shares, render_composed
 
 pytestmark = pytest.mark.gpu
@@ -18,10 +18,6 @@ MAPS = ("rgb_map", "disp_map", "acc_map", "alpha", "T_i", "rgb0", "disp0", "acc0
 
 def T(x, dtype=torch.float32):
     return None if x is None else torch.tensor(np.ascontiguousarray(x), dtype=dtype, device=DEV)
-
-
-def N(t):
-    return t.detach().cpu().numpy()
 
 
 def SP(shift):

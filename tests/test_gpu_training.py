@@ -7,14 +7,10 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import ROOT, golden
+from helpers import ROOT, golden, T
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def T(x, dtype=torch.float32):
-    return torch.tensor(np.ascontiguousarray(x), dtype=dtype, device=DEV)
 
 
 CONFIG_OF = {"danbo_base": ("h36m_zju", "danbo_base.txt"), "danbo_perfcap": ("perfcap", "danbo_fast.txt")}

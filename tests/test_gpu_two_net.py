@@ -8,19 +8,11 @@ import pytest
 import torch
 
 import danbo_oracle as o
-from helpers import ROOT, max_err, raw_err
+from helpers import ROOT, max_err, raw_err, T, N
 from test_two_net_oracle import importance_z_two_net, render_two_net
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def T(x, dtype=torch.float32):
-    return torch.tensor(np.ascontiguousarray(x), dtype=dtype, device=DEV)
-
-
-def N(t):
-    return t.detach().cpu().numpy()
 
 
 # ----------------------------------------------------------------------------- kernels

@@ -1,26 +1,12 @@
 """Image metrics (danbo_image_metrics, --eval_device), the part that needs no GPU: the serial restatement of csrc/metrics_math.hpp
-against the golden SSIM vector and a float64 evaluation, its box semantics, the host arithmetic of scores_from_sums, the exports and
-the binding of include/danbo_metrics.h, the argument checks (which return before any launch) and the new flags."""
-import ctypes
-import os
-import subprocess
-
+against the golden SSIM vector and a float64 evaluation, its box semantics, the host arithmetic of scores_from_sums, the argument
+checks (which return before any launch) and the new flags.  The binding of include/danbo_metrics.h: tests/test_abi_binding.py."""
 import numpy as np
 import pytest
 import torch
 
 import metrics_ref as ref
-from helpers import golden
-
-EINVAL = -22
-# addresses the checks below never follow: every call here returns before a launch (16-byte aligned, not null)
-_BUF = (ctypes.c_float * 64)()
-P = (ctypes.addressof(_BUF) + 15) & ~15
-
-
-def _lib():
-    from core import _hip
-    return _hip.lib()
+from helpers import ADDR as P, EINVAL, golden, hip_lib as _lib     # P: an address no check follows
 
 
 # ----------------------------------------------------------------------------- the serial restatement
@@ -123,56 +109,6 @@ def test_scores_from_sums():
     assert abs(psnr - -10. * np.log10(se[0].mean())) < 1e-12 and abs(ssim - ss[0].mean()) < 1e-12
     psnr, ssim = scores_from_sums((se[0] * mask[0]).sum(), (ss[0] * mask[0]).sum(), mask[0].sum() * 3., guard=False, inf_to_zero=False)
     assert abs(psnr - -10. * np.log10((se[0] * mask[0]).sum() / (mask[0].sum() * 3.))) < 1e-12
-
-
-# ----------------------------------------------------------------------------- exports and binding
-def test_library_exports_and_binding():
-    from core import _hip
-    lib = _lib()
-    raw = ctypes.CDLL(lib._name)
-    Pt, I = ctypes.c_void_p, ctypes.c_int
-    assert os.path.dirname(_hip.METRICS_HEADER_PATH) == os.path.dirname(_hip.HEADER_PATH)
-    assert set(_hip.METRICS_SIGNATURES) == set(_hip.METRICS_RESTYPES) == {"danbo_image_metrics_workspace_bytes", "danbo_image_metrics"}
-    assert not set(_hip.METRICS_SIGNATURES) & (set(_hip.SIGNATURES) | set(_hip.RASTER_SIGNATURES) | set(_hip.PARTMAP_SIGNATURES))
-    assert _hip.METRICS_SIGNATURES["danbo_image_metrics_workspace_bytes"] == [I, I, I]
-    assert _hip.METRICS_SIGNATURES["danbo_image_metrics"] == [Pt] * 5 + [I] * 3 + [Pt, I] + [Pt] * 4
-    assert _hip.METRICS_RESTYPES == {"danbo_image_metrics_workspace_bytes": ctypes.c_size_t, "danbo_image_metrics": I}
-    for name, sig in _hip.METRICS_SIGNATURES.items():
-        assert hasattr(raw, name), name
-        fn = getattr(lib, name)
-        assert fn.restype is _hip.METRICS_RESTYPES[name] and fn.argtypes == sig
-    assert lib.danbo_abi_version() == _hip.C.DANBO_ABI_VERSION == 9
-    with open(_hip.HEADER_PATH) as f:
-        assert "danbo_image_metrics_workspace_bytes, danbo_image_metrics" in f.read()          # the ABI history names them
-    with open(_hip.METRICS_HEADER_PATH) as f:
-        functions, structs, constants = _hip.parse_header(f.read())
-    assert not structs and not constants and set(functions) == set(_hip.METRICS_SIGNATURES)
-
-
-def test_metrics_header_as_the_host_compilers_read_it(tmp_path):
-    """a C compiler accepts the header alone and beside danbo_hip.h, a C++ compiler states the type class of every parameter and
-    result (the referee of tests/test_abi_binding.py, as tests/test_part_maps_host.py applies it to its header)"""
-    from core import _hip
-    inc = os.path.dirname(_hip.METRICS_HEADER_PATH)
-    (tmp_path / "c.c").write_text('#include "danbo_metrics.h"\n#include "danbo_hip.h"\n#include "danbo_metrics.h"\nint main(void) { return 0; }\n')
-    subprocess.check_call(["cc", "-std=c11", "-Wall", "-Werror", "-I", inc, "-o", str(tmp_path / "c"), str(tmp_path / "c.c")])
-    letters = {ctypes.c_void_p: "P", ctypes.c_int: "i", ctypes.c_float: "f", ctypes.c_size_t: "z"}
-    cpp = ['#include <cstdio>', '#include <type_traits>', '#include "danbo_metrics.h"',
-           'template <class T> constexpr char letter() {',
-           "    if constexpr (std::is_pointer_v<T>) return 'P'; else if constexpr (std::is_same_v<T, int>) return 'i';",
-           "    else if constexpr (std::is_same_v<T, float>) return 'f'; else if constexpr (std::is_same_v<T, size_t>) return 'z';",
-           "    else return '?';", '}',
-           'template <class F> struct Sig;',
-           'template <class R, class... A> struct Sig<R(A...)> {',
-           '    static void print(const char* name) { const char args[] = {letter<A>()..., 0}; std::printf("%s %c:%s\\n", name, letter<R>(), args); }',
-           '};', 'int main() {'] + [f'    Sig<decltype({n})>::print("{n}");' for n in _hip.METRICS_SIGNATURES] + ['}']
-    (tmp_path / "s.cpp").write_text("\n".join(cpp))
-    subprocess.check_call(["g++", "-std=c++17", "-I", inc, "-o", str(tmp_path / "s"), str(tmp_path / "s.cpp")])
-    seen = dict(line.split() for line in subprocess.check_output([str(tmp_path / "s")], text=True).splitlines())
-    assert set(seen) == set(_hip.METRICS_SIGNATURES)
-    for name, sig in seen.items():
-        bound = letters[_hip.METRICS_RESTYPES[name]] + ":" + "".join(letters[t] for t in _hip.METRICS_SIGNATURES[name])
-        assert sig == bound, (name, sig, bound)
 
 
 # ----------------------------------------------------------------------------- argument checks

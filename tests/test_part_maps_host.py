@@ -1,71 +1,13 @@
-"""Bone-assignment maps (--render_confd / --render_entropy), the part that needs no GPU: the two entry points of
-csrc/k_partmap.hip are exported and bound, their argument checks return DANBO_EINVAL before any launch, the wrappers refuse CPU
+"""Bone-assignment maps (--render_confd / --render_entropy), the part that needs no GPU: the argument checks of the two entry points
+of csrc/k_partmap.hip return DANBO_EINVAL before any launch (their binding: tests/test_abi_binding.py), the wrappers refuse CPU
 tensors, the command line knows the new flag, and the palette the kernel is handed is the one definition of the joint colours."""
-import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from helpers import golden
-
-EINVAL = -22
-# addresses the checks below never follow: every call here returns before a launch (16-byte aligned, not null)
-_BUF = (ctypes.c_float * 64)()
-P = (ctypes.addressof(_BUF) + 15) & ~15
-
-
-def _lib():
-    from core import _hip
-    return _hip.lib()
-
-
-def test_library_exports_and_binding():
-    """The two entries stand in include/danbo_partmap.h, beside danbo_hip.h (whose entry points tests/test_abi_binding.py pins) and
-    bound by the same parser into tables of their own, as the rasteriser's are."""
-    from core import _hip
-    lib = _lib()
-    raw = ctypes.CDLL(lib._name)
-    P, I = ctypes.c_void_p, ctypes.c_int
-    assert os.path.dirname(_hip.PARTMAP_HEADER_PATH) == os.path.dirname(_hip.HEADER_PATH)
-    assert set(_hip.PARTMAP_SIGNATURES) == set(_hip.PARTMAP_RESTYPES) == {"danbo_part_colors_fwd", "danbo_composite_colors_fwd"}
-    assert not set(_hip.PARTMAP_SIGNATURES) & (set(_hip.SIGNATURES) | set(_hip.RASTER_SIGNATURES))
-    assert _hip.PARTMAP_SIGNATURES["danbo_part_colors_fwd"] == [P, P, P, P, I, I, I, P, P, P]
-    assert _hip.PARTMAP_SIGNATURES["danbo_composite_colors_fwd"] == [P, P, P, P, P, P, I, I, I, P, P, P, P]
-    for name, sig in _hip.PARTMAP_SIGNATURES.items():
-        assert hasattr(raw, name), name
-        fn = getattr(lib, name)
-        assert fn.restype is I and fn.argtypes == sig and _hip.PARTMAP_RESTYPES[name] is I
-    assert lib.danbo_abi_version() == _hip.C.DANBO_ABI_VERSION == 9
-    with open(_hip.HEADER_PATH) as f:
-        assert "danbo_part_colors_fwd, danbo_composite_colors_fwd" in f.read()          # the ABI history names them
-
-
-def test_partmap_header_as_the_host_compilers_read_it(tmp_path):
-    """the referee of tests/test_abi_binding.py for include/danbo_partmap.h: a C compiler accepts it alone and beside danbo_hip.h, a
-    C++ compiler states the type class of every parameter and result"""
-    from core import _hip
-    inc = os.path.dirname(_hip.PARTMAP_HEADER_PATH)
-    (tmp_path / "c.c").write_text('#include "danbo_partmap.h"\n#include "danbo_hip.h"\n#include "danbo_partmap.h"\nint main(void) { return 0; }\n')
-    subprocess.check_call(["cc", "-std=c11", "-Wall", "-Werror", "-I", inc, "-o", str(tmp_path / "c"), str(tmp_path / "c.c")])
-    letters = {ctypes.c_void_p: "P", ctypes.c_int: "i", ctypes.c_float: "f"}
-    cpp = ['#include <cstdio>', '#include <type_traits>', '#include "danbo_partmap.h"',
-           'template <class T> constexpr char letter() {',
-           "    if constexpr (std::is_pointer_v<T>) return 'P'; else if constexpr (std::is_same_v<T, int>) return 'i';",
-           "    else if constexpr (std::is_same_v<T, float>) return 'f'; else return '?';", '}',
-           'template <class F> struct Sig;',
-           'template <class R, class... A> struct Sig<R(A...)> {',
-           '    static void print(const char* name) { const char args[] = {letter<A>()..., 0}; std::printf("%s %c:%s\\n", name, letter<R>(), args); }',
-           '};', 'int main() {'] + [f'    Sig<decltype({n})>::print("{n}");' for n in _hip.PARTMAP_SIGNATURES] + ['}']
-    (tmp_path / "s.cpp").write_text("\n".join(cpp))
-    subprocess.check_call(["g++", "-std=c++17", "-I", inc, "-o", str(tmp_path / "s"), str(tmp_path / "s.cpp")])
-    seen = dict(line.split() for line in subprocess.check_output([str(tmp_path / "s")], text=True).splitlines())
-    assert set(seen) == set(_hip.PARTMAP_SIGNATURES)
-    for name, sig in seen.items():
-        bound = letters[_hip.PARTMAP_RESTYPES[name]] + ":" + "".join(letters[t] for t in _hip.PARTMAP_SIGNATURES[name])
-        assert sig == bound, (name, sig, bound)
+from helpers import ADDR as P, EINVAL, golden, hip_lib as _lib     # P: an address no check follows
 
 
 def part_colors(confd=P, bits=None, lst=None, cnt=None, n=4, mode=0, valid_only=0, palette=P, rgb=P):
