@@ -25,7 +25,8 @@ torch.library.custom_op with register_autograd"), so that a caller -- the refere
 
 All enqueue on the current HIP stream through the C ABI (include/danbo_hip.h); there is no CPU implementation (calling them
 with CPU tensors raises), only shape-propagating fake kernels for tracing.  core/train_path.py (the autograd training path)
-is built on composite / bone_gather; the fused training step (core/train_engine.py) does not need autograd at all.
+is built on pose_volumes / assign_blend / pe_mlp / composite; bone_gather is the materialised part_feat for a caller that wants
+it (the tests' layer-by-layer restatement); the fused training step (core/train_engine.py) does not need autograd at all.
 """
 import ctypes
 from typing import List, Optional, Tuple
@@ -159,8 +160,7 @@ def _pose_params(params):
 
 @torch.library.custom_op("danbo::pose_volumes", mutates_args=())
 def pose_volumes(bones: torch.Tensor, L_graph: int, params: List[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
-    if not bones.is_cuda:
-        raise RuntimeError("danbo::pose_volumes runs on the HIP path only (no CPU fallback)")
+    ops._on_device((bones, "danbo::pose_volumes bones"))
     a, W = _pose_params(params)
     if a["w0"].shape[1] != 6 * (1 + 2 * int(L_graph)):
         raise ValueError(f"danbo::pose_volumes: layer 0 takes {a['w0'].shape[1]} inputs, the rot6d encoding with L = {L_graph} has "
@@ -251,8 +251,7 @@ def _valid_mask(bits, rows):
 @torch.library.custom_op("danbo::assign_blend", mutates_args=())
 def assign_blend(volumes: torch.Tensor, axis_scale: torch.Tensor, pts: torch.Tensor, skts: torch.Tensor, align: torch.Tensor,
                  rows: torch.Tensor, bits: torch.Tensor, params: List[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    if not pts.is_cuda:
-        raise RuntimeError("danbo::assign_blend runs on the HIP path only (no CPU fallback)")
+    ops._on_device((pts, "danbo::assign_blend pts"))
     a = _assign_params(params)
     R = pts.shape[0]
     n = rows.shape[0]
@@ -405,8 +404,7 @@ def _vin_padded(vin):
 
 @torch.library.custom_op("danbo::pe_mlp", mutates_args=())
 def pe_mlp(h: torch.Tensor, row_ray: torch.Tensor, vin: torch.Tensor, params: List[torch.Tensor]) -> torch.Tensor:
-    if not h.is_cuda:
-        raise RuntimeError("danbo::pe_mlp runs on the HIP path only (no CPU fallback)")
+    ops._on_device((h, "danbo::pe_mlp h"))
     params = [p.detach().float().contiguous() for p in params]
     h, vin = h.detach().float().contiguous(), vin.detach().float().contiguous()
     buf, w, r = _trunk_structs(h, row_ray, vin, params, need_bwd=False)
@@ -470,10 +468,7 @@ def pe_mlp_bwd(h: torch.Tensor, row_ray: torch.Tensor, vin: torch.Tensor, params
     mraw = g_raw.detach().abs().max().reshape(1).float().contiguous()
     layers.append(D(dy=d_raw_rows.data_ptr(), ldy=4, N=3, dy_maxabs=mraw.data_ptr(), frag=2, x1=buf["hv"].data_ptr(), ld1=128, K1=128,
                     gw=g[22].data_ptr(), gb=g[23].data_ptr()))
-    L = (D * len(layers))(*layers)
-    slices = 8
-    scratch = torch.empty(_hip.lib().danbo_dw16_scratch_floats(L, len(layers), slices), device=dev)
-    _hip.call("danbo_dw16", L, len(layers), n, _p(buf["cnt"][4:]), slices, _p(scratch), st)
+    ops.dw16(layers, n, dev, buf["cnt"][4:])
     # ---- per-ray view gradients, then the chain rule of the merged feature / view layer
     d_cview = torch.zeros(R, 128, device=dev)
     _hip.call("danbo_train_view_grads", _p(buf["dpre_v"]), _p(buf["row_ray_out"]), _p(buf["cnt"]), n, R, _p(vp), ld, C, None, 0,
@@ -546,8 +541,7 @@ def _anerf_engine(params, align, tau, multires, multires_views):
 def anerf_cutoff_pe_mlp(pts: torch.Tensor, rays_d: torch.Tensor, skts: torch.Tensor, align: torch.Tensor,
                         cam_idx: Optional[torch.Tensor], params: List[torch.Tensor], tau: float, multires: int,
                         multires_views: int) -> torch.Tensor:
-    if not pts.is_cuda:
-        raise RuntimeError("danbo::anerf_cutoff_pe_mlp runs on the HIP path only (no CPU fallback)")
+    ops._on_device((pts, "danbo::anerf_cutoff_pe_mlp pts"))
     eng = _anerf_engine(params, align, tau, multires, multires_views)
     R = pts.shape[0]
     return eng.forward_samples(None, ops._f32(rays_d.reshape(R, 3), "rays_d"), ops._f32(skts, "skts"), cam_idx, pts=ops._f32(pts, "pts")).clone()

@@ -4,12 +4,15 @@ PyTorch is used here for device memory and streams only.  Every function enqueue
 `torch.cuda.current_stream()` and returns without synchronising.  Non-CUDA tensors are
 rejected: there is no CPU fallback.
 """
+import contextlib
 import ctypes
+import gc
 
 import torch
 
 from . import _hip
 from ._hip import call as _call, ptr as _p, stream as _stream  # noqa: F401  (the names the wrappers and the tests use)
+from .utils.skeleton_utils import SMPLSkeleton
 
 # constants of include/danbo_hip.h under the names the wrappers, the engines and the tests use
 J = _hip.C.DANBO_J
@@ -27,11 +30,20 @@ TRUNK_PE_WIDTH = _hip.C.DANBO_TRUNK_PE_WIDTH
 VIEW_W = 128
 
 
+def _on_device(*named, f32=False, dim=None, required=False):
+    """the wrappers' one guard: every (tensor, name) given lives on the device (f32: as float32; dim: with that many
+    dimensions) -- the library reads device memory and nothing else.  None passes unless `required`."""
+    for t, name in named:
+        ok = not required if t is None else t.is_cuda and (not f32 or t.dtype == torch.float32) and (dim is None or t.dim() == dim)
+        if not ok:
+            what = ("%d-D " % dim if dim else "") + ("float32 " if f32 else "")
+            raise RuntimeError(f"{name}: expected a {what}CUDA/HIP tensor -- libdanbo_hip has no CPU fallback")
+
+
 def _f32(t, name):
     if t is None:
         return None
-    if not t.is_cuda:
-        raise RuntimeError(f"{name}: expected a CUDA/HIP tensor -- libdanbo_hip has no CPU fallback")
+    _on_device((t, name))
     if t.dtype != torch.float32:
         t = t.float()
     return t.contiguous()
@@ -90,6 +102,37 @@ def coarse_samples(near, far, S, t_rand=None):
     z = torch.empty(R, S, device=near.device, dtype=torch.float32)
     _call("danbo_coarse_samples", _p(near), _p(far), R, S, _p(_f32(t_rand, "t_rand")), _p(z), _stream())
     return z
+
+
+@contextlib.contextmanager
+def capture(graph):
+    """torch.cuda.graph(graph) with Python's cyclic collector out of the way: garbage is collected before the capture and the
+    collector is off until it ends.  A dead cycle that still holds an older CUDAGraph (a caster's graph cache, an engine) must not
+    be collected DURING a capture: the destructor's HIP calls are not permitted on a capturing thread, its exception cannot leave
+    the destructor, and the process aborts.  torch.cuda.graph collects by itself only under torch.compiler.config.force_cudagraph_gc."""
+    gc.collect()
+    was_on = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph):
+            yield
+    finally:
+        if was_on:
+            gc.enable()
+
+
+def per_pose(x, G):
+    """the G per-pose rows of a per-ray (or already per-pose) tensor: skts / bones / cyls come once per ray from the data loader"""
+    return x if x.shape[0] == G else x[::max(x.shape[0] // G, 1)].contiguous()
+
+
+def dw16(layers, M, device, count=None, slices=8):
+    """danbo_dw16 on a list of _hip.DanboDwLayer: every layer's weight / bias gradient over M rows (count: [1] int32 on the
+    device, the live rows; None: all M) in ONE launch, the rows cut into `slices`; the launch's scratch is allocated here, on
+    `device`: the operands' (the layers carry bare pointers)"""
+    L = (_hip.DanboDwLayer * len(layers))(*layers)
+    scratch = torch.empty(_hip.lib().danbo_dw16_scratch_floats(L, len(layers), slices), device=device)
+    _call("danbo_dw16", L, len(layers), M, _p(count), slices, _p(scratch), _stream())
 
 
 class Geometry:
@@ -206,18 +249,18 @@ def gather_assign_blend(geo, volumes, bits, aw, lst=None, cnt=None, n=None, want
     return h, confd
 
 
-_SMPL_PARENTS = [0, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16, 17, 18, 19, 20, 21]
 _ADJ_CHECKED = set()
 
 
 def check_smpl_adjacency(adj):
-    """k_assign16 (the fp16-split K2 kernel) walks the SMPL tree's neighbour table, compiled in (csrc/k_assign16.hip a16_nb): a
-    checkpoint whose `adj` buffer describes another graph must not be evaluated with it silently.  Checked once per buffer."""
+    """k_assign16 (the fp16-split K2 kernel) walks the SMPL tree's neighbour table, compiled in (csrc/k_assign16.hip a16_nb; the
+    tree of SMPLSkeleton.joint_trees: tests/test_host_logic.py holds the tables to it): a checkpoint whose `adj` buffer describes
+    another graph must not be evaluated with it silently.  Checked once per buffer."""
     key = (adj.data_ptr(), adj._version)
     if key in _ADJ_CHECKED:
         return
     want = torch.eye(J)
-    for i, p_ in enumerate(_SMPL_PARENTS):
+    for i, p_ in enumerate(SMPLSkeleton.joint_trees.tolist()):
         if i != p_:
             want[i, p_] = want[p_, i] = 1.0
     if not torch.equal((adj.detach().reshape(J, J) != 0).cpu(), want != 0):
@@ -555,9 +598,7 @@ def part_colors(confd, mode, rgb, lst=None, cnt=None, n=None, bits=None, valid_o
     bits[m] is set take part (bits: bone_cull's in-volume words, by sample)."""
     if mode not in PART_MODES:
         raise ValueError(f"part_colors: mode must be one of {sorted(PART_MODES)}, not {mode!r}")
-    for t, name in ((confd, "confd"), (rgb, "rgb"), (lst, "list"), (cnt, "count"), (bits, "valid_bits")):
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(f"{name}: expected a CUDA/HIP tensor -- libdanbo_hip has no CPU fallback")
+    _on_device((confd, "confd"), (rgb, "rgb"), (lst, "list"), (cnt, "count"), (bits, "valid_bits"))
     if confd.dtype != torch.float32 or confd.dim() != 2 or confd.shape[1] != J or not confd.is_contiguous():
         raise ValueError("part_colors: confd must be a contiguous [rows, 24] float32 tensor")
     if rgb.dtype != torch.float32 or not rgb.is_contiguous() or rgb.shape[-1] != 3:
@@ -578,9 +619,7 @@ def composite_colors(rgb_a, weights, rgb_b=None, idx=None, bits_a=None, bits_b=N
     from rgb_a [R,S,3] / rgb_b [R,Sf,3] through idx (None, with rgb_b None: the identity).  bits_*: in-volume words of samples
     whose colour rows exist only where the word is not 0.  flat: flat_rays()'s result -- only its listed rays are written; out:
     the [R,3] buffer to write (the frame's rgb_map / rgb0; None: a fresh one)."""
-    for t, name in ((rgb_a, "rgb_a"), (weights, "weights"), (rgb_b, "rgb_b"), (idx, "sorted_idx"), (out, "out")):
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(f"{name}: expected a CUDA/HIP tensor -- libdanbo_hip has no CPU fallback")
+    _on_device((rgb_a, "rgb_a"), (weights, "weights"), (rgb_b, "rgb_b"), (idx, "sorted_idx"), (out, "out"))
     rgb_a, rgb_b, weights = _f32(rgb_a, "rgb_a"), _f32(rgb_b, "rgb_b"), _f32(weights, "weights")
     R, S = rgb_a.shape[:2]
     Sf = 0 if rgb_b is None else rgb_b.shape[1]
@@ -639,9 +678,7 @@ def anerf_view_pe(rays_d, skts, L):
 def transform_batch(vecs, skt, rot_only=False):
     """danbo_transform_batch_pts: vecs [N, S, 3] (points; rot_only: directions) into the local frame of every joint of skt
     [G, J, 4, 4] with G dividing N (ray r belongs to pose r // (N // G)) -> [N, S, J, 3]"""
-    for t, nm in ((vecs, "pts"), (skt, "skt")):
-        if not t.is_cuda or t.dtype != torch.float32:
-            raise RuntimeError(f"transform_batch {nm}: expected a float32 CUDA/HIP tensor -- libdanbo_hip has no CPU fallback")
+    _on_device((vecs, "transform_batch pts"), (skt, "transform_batch skt"), f32=True)
     N, S = vecs.shape[:2]
     G, J = skt.shape[0], skt.shape[-3]
     if vecs.shape[-1] != 3 or skt.shape[-2:] != (4, 4) or G < 1 or N % G:
@@ -655,8 +692,8 @@ def transform_batch(vecs, skt, rot_only=False):
 def optcodes(codes, idx, mode):
     """danbo_optcodes_fwd: mode 0 rows codes[idx[:, 0]] (clamped), 1 the mean code per row of idx, 2 lerp(codes[idx[:, 0]],
     codes[idx[:, 1]], idx[:, 2]) -> [N, code_ch]"""
-    if not codes.is_cuda or codes.dtype != torch.float32 or not idx.is_cuda:
-        raise RuntimeError("optcodes: expected CUDA/HIP tensors -- libdanbo_hip has no CPU fallback")
+    _on_device((codes, "optcodes codes"), f32=True)
+    _on_device((idx, "optcodes idx"))
     idx = idx.reshape(idx.shape[0], -1).to(torch.float32).contiguous()
     codes = codes.contiguous()
     out = torch.empty(idx.shape[0], codes.shape[1], device=codes.device, dtype=torch.float32)
@@ -668,9 +705,7 @@ def small_matmul(a, b, bias=None, out=None):
     """a [M, K] @ b [K, N] (+ bias [N]) -> float32 [M, N]; a, b: float32 CUDA tensors of ANY strides (slices and .t() views are read
     in place); the sum over k accumulated in float64 and rounded once (danbo_small_matmul: one thread per output -- the
     parameter-sized products of a weight refresh, which were float64 torch matmuls, i.e. library GEMMs, until round 5)"""
-    for t, nm in ((a, "a"), (b, "b")):
-        if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2:
-            raise RuntimeError(f"small_matmul {nm}: expected a 2-D float32 CUDA/HIP tensor -- libdanbo_hip has no CPU fallback")
+    _on_device((a, "small_matmul a"), (b, "small_matmul b"), f32=True, dim=2)
     M, K = a.shape
     K2, N = b.shape
     if K != K2:
@@ -719,8 +754,7 @@ def anerf_view_consts_bwd(rays_d, skts, L, dC, g_views_w, col0):
 
 def _rows(t, name):
     """fp32 CUDA matrix whose rows may be strided (a column slice of a wider buffer) -> (tensor, row stride in floats)"""
-    if not t.is_cuda or t.dtype != torch.float32:
-        raise RuntimeError(f"{name}: expected a float32 CUDA/HIP tensor -- libdanbo_hip has no CPU fallback")
+    _on_device((t, name), f32=True)
     if t.dim() == 1:
         t = t.unsqueeze(1)
     if t.stride(1) != 1:
@@ -929,8 +963,7 @@ def marching_cubes(sigma, iso, floor=float("-inf"), scale=1.0, offset=(0.0, 0.0,
     normals from inside to outside.  One host read (the two counts) sizes the outputs; an empty surface launches nothing more.
     normals=True: -> verts, faces, normals [V,3] float32 -- the unit normal at every vertex (danbo_mesh_normals: the normalised
     negative gradient of the floored grid, in index space whatever scale and offset are), one more launch on the same workspace."""
-    if not sigma.is_cuda:
-        raise RuntimeError("sigma: expected a CUDA/HIP tensor -- libdanbo_hip has no CPU fallback")
+    _on_device((sigma, "sigma"))
     if sigma.dtype != torch.float32 or sigma.dim() != 3:
         raise ValueError("marching_cubes: sigma must be a [nx, ny, nz] float32 grid")
     if sigma.stride(2) != 1:
@@ -974,9 +1007,7 @@ def rasterize_mesh(verts, faces, attr=None, mode="normal", views=None, half_exte
     not culled, one sample per pixel; deterministic: two calls give the same bits.
     -> dict of the outputs named in `want`: 'rgb' [n,H,W,3] float32, 'depth' [n,H,W] float32 (-inf: background), 'tri_id' [n,H,W]
     int32 (-1: background).  Enqueues 4 launches per view on the current stream; no synchronisation."""
-    for t, name in ((verts, "verts"), (faces, "faces"), (views, "views")):
-        if t is None or not t.is_cuda:
-            raise RuntimeError(f"{name}: expected a CUDA/HIP tensor -- libdanbo_hip has no CPU fallback")
+    _on_device((verts, "verts"), (faces, "faces"), (views, "views"), required=True)
     if mode not in RASTER_MODES:
         raise ValueError(f"rasterize_mesh: mode must be one of {sorted(RASTER_MODES)}, not {mode!r}")
     if verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
@@ -995,8 +1026,7 @@ def rasterize_mesh(verts, faces, attr=None, mode="normal", views=None, half_exte
     else:
         if attr is None:
             raise ValueError(f"rasterize_mesh: mode {mode!r} needs attr [V, 3]")
-        if not attr.is_cuda:
-            raise RuntimeError("attr: expected a CUDA/HIP tensor -- libdanbo_hip has no CPU fallback")
+        _on_device((attr, "attr"))
         if attr.dtype != torch.float32 or tuple(attr.shape) != (V, 3):
             raise ValueError(f"rasterize_mesh: attr must be a [{V}, 3] float32 tensor")
         attr = attr.contiguous() if V else attr.new_zeros(1, 3)         # (the library wants a pointer even where it reads nothing)
@@ -1044,9 +1074,7 @@ def image_metrics(pred, gt, mask_a=None, mask_b=None, boxes=None, want_map=False
     crop, zero padded.  -> dict(sums=[N,8] float32: S se, S ssim, S se a, S ssim a, S a, S se b, S ssim b, S b (the slots of a mask
     that is None: 0), ssim_map=[N,H,W,3] inside the boxes (0 outside) or None).  Two launches on the current stream, no
     synchronisation; the same bits on every call.  The window is cached per device, the workspace per device, size and stream."""
-    for t, name in ((pred, "pred"), (gt, "gt"), (mask_a, "mask_a"), (mask_b, "mask_b"), (boxes, "boxes")):
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(f"{name}: expected a CUDA/HIP tensor -- libdanbo_hip has no CPU fallback")
+    _on_device((pred, "pred"), (gt, "gt"), (mask_a, "mask_a"), (mask_b, "mask_b"), (boxes, "boxes"))
     if pred.dim() != 4 or pred.shape[-1] != 3 or pred.shape != gt.shape:
         raise ValueError("image_metrics: pred and gt must be [N, H, W, 3] tensors of one shape")
     pred, gt = _f32(pred, "pred"), _f32(gt, "gt")

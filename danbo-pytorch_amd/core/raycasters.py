@@ -267,9 +267,7 @@ class RayCaster(nn.Module):
             return {}
         return dict(part_map='confd' if render_confd else 'entropy', part_valid_only=bool(part_valid_only))
 
-    @staticmethod
-    def _per_pose(x, G):
-        return x if x.shape[0] == G else x[::max(x.shape[0] // G, 1)].contiguous()
+    _per_pose = staticmethod(ops.per_pose)
 
     def render_rays(self, ray_batch, N_samples, kp_batch, skts=None, cyls=None, bones=None, cams=None,
                     subject_idxs=None, retraw=False, lindisp=False, perturb=0., N_importance=0, network_fine=None,
@@ -496,7 +494,7 @@ class _ChainGraph:
             chain(*self.inputs)
         cur.wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
+        with ops.capture(self.graph):
             out = chain(*self.inputs)
             self.keys = list(out)
             self.shapes = [tuple(out[k].shape) for k in self.keys]

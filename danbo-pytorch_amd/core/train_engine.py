@@ -420,12 +420,12 @@ class DanboTrainEngine:
             cur.wait_stream(side)
             # keep_graph: the captured hipGraph_t stays inspectable (raw_cuda_graph(); tests walk its edges: nothing may run beside K2)
             g = torch.cuda.CUDAGraph(keep_graph=True) if getattr(self, 'keep_graph', False) else torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
+            with hip_ops.capture(g):
                 outs = self._launch(static, S, Sf, perturb, raw_noise_std, split)
             g2 = None
             if second:                            # the weight-gradient GEMMs as their own graph: the all-reduce of the finished
                 g2 = torch.cuda.CUDAGraph()       # gradients is launched between the two replays
-                with torch.cuda.graph(g2):
+                with hip_ops.capture(g2):
                     self._step_phase(outs, 2)
             self.graph = (key, g, static, outs, g2)
             if rng_before is not None:            # a run's random stream does not depend on when (or how often) a graph was built

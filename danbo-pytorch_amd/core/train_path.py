@@ -34,32 +34,6 @@ from ._hip import ptr as _p
 # --------------------------------------------------------------------------------------
 # custom autograd functions around the HIP kernels
 # --------------------------------------------------------------------------------------
-class GatherFn(torch.autograd.Function):
-    """part_feat [n,24,15] = factorised gather of `volumes` at the listed samples (K1b)."""
-
-    @staticmethod
-    def forward(ctx, volumes, axis_scale, geo, rows):
-        geo.axis_scale = axis_scale.detach().float().contiguous()
-        n = rows.shape[0]
-        out = ops.bone_gather(geo, volumes.detach().contiguous(), rows, None, n)
-        ctx.geo, ctx.n = geo, n
-        ctx.save_for_backward(volumes.detach(), geo.axis_scale, rows)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        volumes, axis_scale, rows = ctx.saved_tensors
-        geo = ctx.geo
-        # explicit shapes: zeros_like would inherit the permuted strides of an einsum output
-        d_vol = torch.zeros(volumes.shape, dtype=torch.float32, device=volumes.device)
-        d_sc = torch.zeros(axis_scale.shape, dtype=torch.float32, device=volumes.device)
-        g = g.contiguous().float()
-        if ctx.n > 0:
-            _hip.call("danbo_bone_gather_bwd", _p(geo.rays_o), _p(geo.rays_d), _p(geo.z), _p(geo.pts), geo.R, geo.S, geo.G, _p(geo.skts),
-                      _p(geo.align), _p(axis_scale), _p(volumes.contiguous()), _p(rows), ctx.n, _p(g), _p(d_vol), _p(d_sc), ops._stream())
-        return d_vol, d_sc, None, None
-
-
 def _packed(weight, K1=None, transposed=False, cols=None):
     """fragment packing of a dense-layer weight for Linear16Fn; cols = (c0, c1): of the column slice weight[:, c0:c1].  Cached ON
     the parameter object, per version counter (an optimizer step re-packs; a new tensor at a recycled address cannot hit)"""
@@ -127,10 +101,7 @@ class Linear16Fn(torch.autograd.Function):
         layers = [D(x1=x1.data_ptr(), ld1=K1, K1=K1, gw_col0=0, gb=gb.data_ptr(), **common)]
         if K2:      # the second input as a layer of its own writing its column range of the same weight gradient
             layers.append(D(x1=x2.data_ptr(), ld1=K2, K1=K2, gw_col0=K1, gb=None, **common))
-        L = (D * len(layers))(*layers)
-        slices = 8
-        scratch = torch.empty(_hip.lib().danbo_dw16_scratch_floats(L, len(layers), slices), device=dz.device)
-        _hip.call("danbo_dw16", L, len(layers), M, None, slices, _p(scratch), ops._stream())
+        ops.dw16(layers, M, dz.device)
         return dx1, dx2, gw, (gb if ctx.has_bias else None), None, None
 
 
@@ -339,8 +310,7 @@ def forward_train(model, inputs):
     R, S = pts.shape[:2]
     G = int(inputs.get("N_uniques", 1))
     skts, bones = inputs["skts"], inputs["bones"]
-    skts_g = (skts if skts.shape[0] == G else skts[:: max(skts.shape[0] // G, 1)]).contiguous().float()
-    bones_g = (bones if bones.shape[0] == G else bones[:: max(bones.shape[0] // G, 1)]).contiguous().float()
+    skts_g, bones_g = ops.per_pose(skts, G).contiguous().float(), ops.per_pose(bones, G).contiguous().float()
     align = inputs["align_transforms"].reshape(-1, 24, 4, 4)[0].contiguous().float().to(pts.device)
     rays_d = inputs["rays_d"].reshape(R, 3).contiguous().float()
     axis_scale = model.graph_net.axis_scale
@@ -413,7 +383,7 @@ def forward_train_anerf(model, inputs):
     R, S = pts.shape[:2]
     G = int(inputs.get("N_uniques", 1))
     skts = inputs["skts"]
-    skts_g = (skts if skts.shape[0] == G else skts[:: max(skts.shape[0] // G, 1)]).contiguous().float()
+    skts_g = ops.per_pose(skts, G).contiguous().float()
     align = inputs["align_transforms"].reshape(-1, 24, 4, 4)[0].contiguous().float().to(pts.device)
     rays_d = inputs["rays_d"].reshape(R, 3).contiguous().float()
     L, Lv = model.pe_fn.num_freqs, model.dirs_pe_fn.num_freqs

@@ -32,8 +32,8 @@ def turntable_views(verts, n_frames=N_FRAMES, step_deg=STEP_DEG):
     float32 on its device: frame j is  Ry(-(90 + step_deg (j + 1)) degrees) * s * base_rotation(), s = 1 / (y_max - y_min) of the
     rotated vertices -- the mesh is scaled to unit height and NOT centred, as in the reference -- with no translation.  Float64
     in closed form, rounded once to float32; the two extrema are one reduction on the device (one host read)."""
-    if not verts.is_cuda:
-        raise RuntimeError("verts: expected a CUDA/HIP tensor -- libdanbo_hip has no CPU fallback")
+    from core import hip_ops
+    hip_ops._on_device((verts, "verts"))
     if verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] == 0:
         raise ValueError("turntable_views: verts must be a non-empty [V, 3] tensor")
     B = base_rotation()

@@ -11,6 +11,10 @@
 // the density activation of an `_act` entry point (danbo_hip.h): a known type and a finite shift, before any launch
 #define DANBO_CHECK_DENSITY_ACT(act, shift) \
     DANBO_CHECK_ARG(((act) == DANBO_DENSITY_RELU || (act) == DANBO_DENSITY_SOFTPLUS) && (shift) - (shift) == 0.f)
+// what entry points share: R rays of G poses with equally many rays each; an [R, S] batch of their samples; exactly one of z / pts
+static inline bool poses_ok(int R, int G) { return R > 0 && G > 0 && R % G == 0; }
+static inline bool shape_ok(int R, int S, int G) { return S > 0 && poses_ok(R, G); }
+static inline bool one_of(const void* z, const void* pts) { return (z == nullptr) != (pts == nullptr); }
 // a C call made of C calls: the first non-zero return code is the caller's
 #define DANBO_TRY(call) do { const int rc_ = (call); if (rc_ != 0) return rc_; } while (0)
 #define DANBO_LAUNCH_RET() do { hipError_t e_ = hipGetLastError(); return e_ == hipSuccess ? 0 : (int)e_; } while (0)
@@ -54,6 +58,7 @@ typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
 // Compute units of the calling thread's current device (hipDeviceAttributeMultiprocessorCount, cached per device): the
 // persistent kernels size their grids from it.  256 on a full MI355X; partitioned (CPX / DPX) or harvested parts report less.
 // Development switches (fault bisection, stream-order experiments, A/B of a packing) read the environment only in a
@@ -220,6 +225,16 @@ static __global__ __launch_bounds__(64) void k_copy_words_(const uint32_t* __res
                                                            const uint32_t* __restrict__ s1, uint32_t* __restrict__ d1, int n1) {
     for (int i = threadIdx.x; i < n0; i += 64) d0[i] = s0[i];
     for (int i = threadIdx.x; i < n1; i += 64) d1[i] = s1[i];
+}
+
+// The per-bone tables the gather / cull / assignment kernels keep in LDS, staged by a workgroup of BLOCK threads (the caller's
+// barrier follows): align [24][16], and |axis_scale| as [24][4] rows whose fourth entry is `pad` -- 0 where only in_volume reads
+// the row, 1 where the row is also divided by
+template <int BLOCK>
+__device__ __forceinline__ void stage_bone_tables(const float* __restrict__ align, const float* __restrict__ axis_scale,
+                                                  float* s_align, float* s_scale, float pad) {
+    for (int i = threadIdx.x; i < J * 16; i += BLOCK) s_align[i] = align[i];
+    for (int i = threadIdx.x; i < J * 4; i += BLOCK) s_scale[i] = (i & 3) < 3 ? fabsf(axis_scale[(i >> 2) * 3 + (i & 3)]) : pad;
 }
 
 // number of rows a kernel has to process: device-side count (clamped to capacity) or host n

@@ -91,7 +91,7 @@ __device__ __forceinline__ void composite_fwd_sweep(const float4* __restrict__ r
             carry = mul_rn(carry, __shfl(p, 63, 64));
         }
         rr[c] = sigmoidf_(rw.x); rg[c] = sigmoidf_(rw.y); rb[c] = sigmoidf_(rw.z);
-        cr[c] = rgb_affine(rr[c]); cg[c] = rgb_affine(rg[c]); cb[c] = rgb_affine(rb[c]);
+        cr[c] = sigmoid_affine(rr[c]); cg[c] = sigmoid_affine(rg[c]); cb[c] = sigmoid_affine(rb[c]);
         acc += wave_sum(act ? a * T[c] : 0.f);
     }
     st.acc = acc;
@@ -134,9 +134,9 @@ __device__ __forceinline__ void composite_bwd_sweep(const CompositeState<NC>& st
                 dads = sig[c] > 0.f ? dist[c] * expf(-sig[c] * dist[c]) : 0.f;
             }
             float4 o;
-            o.x = gr * w * 1.002f * rr[c] * (1.0f - rr[c]);
-            o.y = gg * w * 1.002f * rg[c] * (1.0f - rg[c]);
-            o.z = gb * w * 1.002f * rb[c] * (1.0f - rb[c]);
+            o.x = sigmoid_affine_bwd(gr * w, rr[c]);
+            o.y = sigmoid_affine_bwd(gg * w, rg[c]);
+            o.z = sigmoid_affine_bwd(gb * w, rb[c]);
             o.w = dLda * dads / B;
             out(s, o);
         }

@@ -8,6 +8,14 @@ namespace danbo {
 
 typedef float v2f __attribute__((ext_vector_type(2)));
 
+// li / S with inv_S = 1 / (float)S, exact for li < 2^22: the ray of a workgroup's local sample index without an integer division
+__device__ __forceinline__ int ray_of_local(int li, int S, float inv_S) {
+    int q = (int)((float)li * inv_S);
+    q -= (q * S > li) ? 1 : 0;
+    q += ((q + 1) * S <= li) ? 1 : 0;
+    return q;
+}
+
 // ((m0*x + m1*y) + m2*z) + m3 for two points at once; every packed op rounds each half like the
 // scalar __fmul_rn / __fadd_rn chain of affine_unfused() (contraction disabled).
 // The matrix entries are BROADCAST over the pair.  Left to the compiler that is v_pk_mul_f32 x, m op_sel:[0,1] for the odd entries --

@@ -55,8 +55,9 @@ __global__ __launch_bounds__(AN_BLOCK) void k_anerf_encode(const float* __restri
         const int row = (tile * SUB + sub) * AN_TS + sl;
         if (row < nrows) {
             const long m = row0 + row;
-            const int g = (int)min(m / spp, (long)G - 1);
+            const int g = pose_of_sample(m, spp, G);
             float p[3], pt[3], sk[12];
+            // point_of_sample (sample_math.hpp), restated: the call moved both instantiations (profiles/per_sample_definitions_measured.txt)
             if (pts) { p[0] = pts[3 * m]; p[1] = pts[3 * m + 1]; p[2] = pts[3 * m + 2]; }
             else {
                 const long r = m / S;
@@ -135,9 +136,9 @@ using namespace danbo;
 static int anerf_encode_impl(const float* rays_o, const float* rays_d, const float* z, const float* pts, int R,
                              int S, int G, const float* skts, const float* align, const float* cutoff, float tau, const float* tau_dev,
                              int L, long row0, int nrows, float* x0, float* w_out, void* stream) {
-    DANBO_CHECK_ARG(R > 0 && S > 0 && G > 0 && R % G == 0 && L >= 0 && L <= AN_MAXL && nrows >= 0 && row0 >= 0);
+    DANBO_CHECK_ARG(L >= 0 && L <= AN_MAXL && nrows >= 0 && row0 >= 0 && shape_ok(R, S, G));
     DANBO_CHECK_ARG(row0 + nrows <= (long)R * S && skts && align && cutoff && x0 && w_out);
-    DANBO_CHECK_ARG((z == nullptr) != (pts == nullptr) && (pts || (rays_o && rays_d)));
+    DANBO_CHECK_ARG(one_of(z, pts) && (pts || (rays_o && rays_d)));
     if (nrows == 0) return 0;
     const int in_ch = (1 + 2 * L) * J + 3 * J;
     const int ntiles = ceil_div(nrows, AN_TS);
@@ -165,9 +166,9 @@ extern "C" int danbo_anerf_encode_fwd_dtau(const float* rays_o, const float* ray
 extern "C" int danbo_anerf_encode_compact(const float* rays_o, const float* rays_d, const float* z, const float* pts, int R,
                                           int S, int G, const float* skts, const float* align, const float* cutoff, float tau,
                                           long row0, int nrows, float* table, float* w_out, void* stream) {
-    DANBO_CHECK_ARG(R > 0 && S > 0 && G > 0 && R % G == 0 && nrows >= 0 && row0 >= 0);
+    DANBO_CHECK_ARG(nrows >= 0 && row0 >= 0 && shape_ok(R, S, G));
     DANBO_CHECK_ARG(row0 + nrows <= (long)R * S && skts && align && cutoff && table && w_out && (uintptr_t)table % 16 == 0);
-    DANBO_CHECK_ARG((z == nullptr) != (pts == nullptr) && (pts || (rays_o && rays_d)));
+    DANBO_CHECK_ARG(one_of(z, pts) && (pts || (rays_o && rays_d)));
     if (nrows == 0) return 0;
     const int ntiles = ceil_div(nrows, AN_TS * AN_SUB);
     const int grid = ntiles < num_cu() * 8 ? ntiles : num_cu() * 8;
@@ -177,7 +178,7 @@ extern "C" int danbo_anerf_encode_compact(const float* rays_o, const float* rays
 }
 
 extern "C" int danbo_anerf_view_pe_fwd(const float* rays_d, const float* skts, int R, int G, int L, float* E, void* stream) {
-    DANBO_CHECK_ARG(R > 0 && G > 0 && R % G == 0 && L >= 0 && L <= AN_MAXL && rays_d && skts && E);
+    DANBO_CHECK_ARG(L >= 0 && L <= AN_MAXL && rays_d && skts && E && poses_ok(R, G));
     hipLaunchKernelGGL(k_anerf_view_pe, dim3(stream_grid((long)R * J, 256)), dim3(256), 0, (hipStream_t)stream, rays_d,
                        skts, R, G, L, E);
     DANBO_LAUNCH_RET();

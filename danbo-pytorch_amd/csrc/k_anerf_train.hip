@@ -472,7 +472,7 @@ extern "C" int danbo_anerf_view_wj_pack(const float* views_w, int ld, int col0, 
 
 extern "C" int danbo_anerf_view_consts_fwd(const float* rays_d, const float* skts, int R, int G, int L, const float* wj, int VW, float* C,
                                            void* stream) {
-    DANBO_CHECK_ARG(rays_d && skts && wj && C && R > 0 && G > 0 && R % G == 0 && L >= 0 && L <= 8 && VW >= 1 && VW <= AV_VW_MAX);
+    DANBO_CHECK_ARG(rays_d && skts && wj && C && L >= 0 && L <= 8 && VW >= 1 && VW <= AV_VW_MAX && poses_ok(R, G));
     const int ntiles = ceil_div(R, AV_TR);
     const int gx = ntiles < num_cu() ? ntiles : num_cu();       // x 24 joints: a few workgroups per CU
     if (L == 4) {
@@ -496,7 +496,7 @@ extern "C" long danbo_anerf_view_consts_bwd_scratch_floats(int R, int L, int VW)
 }
 extern "C" int danbo_anerf_view_consts_bwd(const float* rays_d, const float* skts, int R, int G, int L, const float* dC, int VW,
                                            float* g_views_w, int ld, int col0, float* scratch, void* stream) {
-    DANBO_CHECK_ARG(rays_d && skts && dC && g_views_w && scratch && R > 0 && G > 0 && R % G == 0 && L >= 0 && L <= 8);
+    DANBO_CHECK_ARG(rays_d && skts && dC && g_views_w && scratch && L >= 0 && L <= 8 && poses_ok(R, G));
     DANBO_CHECK_ARG(VW >= 1 && VW <= AV_VW_MAX && col0 >= 0 && ld >= col0 + 72 * (1 + 2 * L));
     const int slices = av_bwd_slices(R), nk = 3 * (1 + 2 * L);
     if (L == 4) {

@@ -22,7 +22,7 @@ constexpr int ASSIGN_LDS_FLOATS = W0P + W1P + W2P + W2P /*b1*/ + AW /*b0*/ + J /
 
 // SMPL kinematic tree (core/utils/skeleton_utils.py:83-110): parent of each joint
 __device__ __constant__ int8_t c_parent[J] = {0, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16, 17, 18, 19, 20, 21};
-// up to four graph neighbours (parent + children), -1 padded
+// up to four graph neighbours (parent + children), -1 padded (tests/test_host_logic.py holds both to SMPLSkeleton.joint_trees)
 __device__ __constant__ int8_t c_nbr[J][4] = {
     {1, 2, 3, -1},  {0, 4, -1, -1},  {0, 5, -1, -1},  {0, 6, -1, -1},  {1, 7, -1, -1},  {2, 8, -1, -1},
     {3, 9, -1, -1}, {4, 10, -1, -1}, {5, 11, -1, -1}, {6, 12, 13, 14}, {7, -1, -1, -1}, {8, -1, -1, -1},
@@ -80,9 +80,7 @@ __global__ __launch_bounds__(ASSIGN_BLOCK) void k_assign_blend(
         s_b1[((c >> 2) * J + j) * 4 + (c & 3)] = b1[i];
     }
     if (FUSED) {
-        for (int i = tid; i < J * 16; i += ASSIGN_BLOCK) s_align[i] = ga.align[i];
-        for (int i = tid; i < J * 4; i += ASSIGN_BLOCK)
-            s_scale[i] = (i & 3) < 3 ? fabsf(ga.axis_scale[(i >> 2) * 3 + (i & 3)]) : 1.f;
+        stage_bone_tables<ASSIGN_BLOCK>(ga.align, ga.axis_scale, s_align, s_scale, 1.f);
     }
     if (tid < AW) s_b0[tid] = b0[tid];
     if (tid < J) {
@@ -123,16 +121,9 @@ __global__ __launch_bounds__(ASSIGN_BLOCK) void k_assign_blend(
         const int m = list ? list[rowc] : rowc;
         if (FUSED) {
             const long spp = (long)(ga.R / ga.G) * ga.S;
-            const int g = (int)min((long)m / spp, (long)ga.G - 1);
+            const int g = pose_of_sample(m, spp, ga.G);
             float p[3], pt[3], sk[12];
-            if (ga.pts != nullptr) {
-                p[0] = ga.pts[3 * (size_t)m]; p[1] = ga.pts[3 * (size_t)m + 1]; p[2] = ga.pts[3 * (size_t)m + 2];
-            } else {
-                const int r = m / ga.S;
-                const float o[3] = {ga.rays_o[3 * r], ga.rays_o[3 * r + 1], ga.rays_o[3 * r + 2]};
-                const float d[3] = {ga.rays_d[3 * r], ga.rays_d[3 * r + 1], ga.rays_d[3 * r + 2]};
-                sample_point(o, d, ga.z[m], p);
-            }
+            point_of_sample(ga.rays_o, ga.rays_d, ga.z, ga.pts, m, ga.S, p);
             const float* src = ga.skts + ((size_t)g * J + j) * 16;
 #pragma unroll
             for (int i = 0; i < 12; ++i) sk[i] = src[i];
@@ -226,7 +217,7 @@ __global__ __launch_bounds__(ASSIGN_BLOCK) void k_assign_blend(
         // ---- masked sigmoid + blend ----
         const uint32_t bits = valid_bits[m];
         const float valid = (bone_ok && ((bits >> j) & 1u)) ? 1.0f : 0.0f;
-        const float p = (sigmoidf_(a) * 1.002f - 0.001f) * valid;
+        const float p = sigmoid_affine(sigmoidf_(a)) * valid;
         float hsum[FEAT];
 #pragma unroll
         for (int k = 0; k < FEAT; ++k) {
@@ -283,8 +274,7 @@ extern "C" int danbo_gather_assign_blend_fwd(const float* rays_o, const float* r
                                               int n, const float* w0, const float* adjw, const float* b0,
                                               const float* w1, const float* b1, const float* w2, const float* b2,
                                               float* h, float* confd, void* stream) {
-    DANBO_CHECK_ARG(n >= 0 && valid_bits && h && R > 0 && S > 0 && G > 0 && R % G == 0);
-    DANBO_CHECK_ARG((z == nullptr) != (pts == nullptr));
+    DANBO_CHECK_ARG(n >= 0 && valid_bits && h && shape_ok(R, S, G) && one_of(z, pts));
     if (n == 0) return 0;
     GatherArgs ga = {rays_o, rays_d, z, pts, R, S, G, skts, align, axis_scale, volumes};
     return launch_assign<true>(ga, nullptr, valid_bits, list, count, n, w0, adjw, b0, w1, b1, w2, b2, h, confd, stream);

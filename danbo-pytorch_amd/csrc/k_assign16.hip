@@ -21,7 +21,7 @@ constexpr int A16_NCHUNK = 8;  // 236 pieces of 1 KB, padded to 256
 static_assert(A16_NCHUNK * A16_CHUNK == DANBO_ASSIGN16_PACKED_BYTES, "header constant out of date");
 constexpr int A16_BM = 128;    // samples per workgroup iteration (4 wavefronts x 32)
 
-// SMPL tree neighbours (parent + children), the bone itself first
+// SMPL tree neighbours (parent + children), the bone itself first (tests/test_host_logic.py holds them to SMPLSkeleton.joint_trees)
 __host__ __device__ constexpr int a16_deg(int j) {
     constexpr int d[J] = {3, 2, 2, 2, 2, 2, 2, 2, 2, 4, 1, 1, 2, 2, 2, 1, 2, 2, 2, 2, 2, 2, 1, 1};
     return d[j];
@@ -267,11 +267,8 @@ __global__ __launch_bounds__(256, 2) void k_assign16(A16Args a) {
         s_w2[i] = a.w2[i] * f[3];
     }
     if (tid < J) s_b2[tid] = a.b2[tid];
-    for (int i = tid; i < J * 16; i += 256) s_align[i] = a.align[i];
-    for (int i = tid; i < J * 4; i += 256) {
-        s_scale[i] = (i & 3) < 3 ? fabsf(a.axis_scale[(i >> 2) * 3 + (i & 3)]) : 1.f;
-        s_inv[i] = div_rn(1.0f, s_scale[i]);
-    }
+    stage_bone_tables<256>(a.align, a.axis_scale, s_align, s_scale, 1.f);
+    for (int i = tid; i < J * 4; i += 256) s_inv[i] = div_rn(1.0f, s_scale[i]);     // (entry i is this thread's own store)
     if (tid < J) {
 #pragma unroll
         for (int jj = 0; jj < J; ++jj)
@@ -393,6 +390,7 @@ __global__ __launch_bounds__(256, 2) void k_assign16(A16Args a) {
         const bool row_ok = row < n;
         const int ms = cur.ms;
         const uint32_t bits = cur.bits;
+        // pose_of_sample (sample_math.hpp) in 32-bit unsigned arithmetic, here and for g_tile: no 64-bit division per row
         const int g = multi_pose ? (int)min((unsigned)ms / spp32, (unsigned)a.G - 1u) : 0;
         float pnt[3];
         if (a.pts != nullptr) { pnt[0] = cur.o[0]; pnt[1] = cur.o[1]; pnt[2] = cur.o[2]; }
@@ -565,7 +563,7 @@ __global__ __launch_bounds__(256, 2) void k_assign16(A16Args a) {
             const float valid = ((bits >> j) & 1u) ? 1.0f : 0.0f;
             // sigmoid through v_exp_f32 / v_rcp_f32 (1 ulp each; p enters h = sum p_j f_j, compared at 5e-6)
             const float sg = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(logit * -1.44269504088896340736f));
-            const float pj = (sg * 1.002f - 0.001f) * valid;
+            const float pj = sigmoid_affine(sg) * valid;
 #pragma unroll
             for (int e = 0; e < 8; ++e) hacc[e] = fmaf(pj, fself[e], hacc[e]);
             if (TRAIN) qsum += pj;
@@ -608,6 +606,15 @@ extern "C" int danbo_assign16_pack(const float* w0, const float* adjw, const flo
     DANBO_LAUNCH_RET();
 }
 
+template <bool TRAIN>
+static int launch_assign16(const A16Args& a, int n, void* stream) {
+    DANBO_ENSURE_LDS(k_assign16<TRAIN>, A16_LDS_BYTES);
+    const int ntiles = ceil_div(n, A16_BM);
+    const int grid = ntiles < 2 * num_cu() ? ntiles : 2 * num_cu();
+    hipLaunchKernelGGL(k_assign16<TRAIN>, dim3(grid), dim3(256), A16_LDS_BYTES, (hipStream_t)stream, a);
+    DANBO_LAUNCH_RET();
+}
+
 extern "C" int danbo_gather_assign_blend16_fwd(const float* rays_o, const float* rays_d, const float* z,
                                                 const float* pts, int R, int S, int G, const float* skts,
                                                 const float* align, const float* axis_scale, const float* volumes,
@@ -615,16 +622,11 @@ extern "C" int danbo_gather_assign_blend16_fwd(const float* rays_o, const float*
                                                 int n, const void* packed16, const float* b0, const float* b1,
                                                 const float* w2, const float* b2, float* h, float* confd,
                                                 uint32_t* ticket, void* stream) {
-    DANBO_CHECK_ARG(n >= 0 && valid_bits && h && packed16 && ticket && R > 0 && S > 0 && G > 0 && R % G == 0);
-    DANBO_CHECK_ARG((z == nullptr) != (pts == nullptr));
+    DANBO_CHECK_ARG(n >= 0 && valid_bits && h && packed16 && ticket && shape_ok(R, S, G) && one_of(z, pts));
     if (n == 0) return 0;
     A16Args a = {rays_o, rays_d, z, pts, R, S, G, skts, align, axis_scale, volumes, valid_bits, list, count, n,
                  reinterpret_cast<const char*>(packed16), b0, b1, w2, b2, h, confd, nullptr, g_a16_trace, ticket, a16_no_skip()};
-    DANBO_ENSURE_LDS(k_assign16<false>, A16_LDS_BYTES);
-    const int ntiles = ceil_div(n, A16_BM);
-    const int grid = ntiles < 2 * num_cu() ? ntiles : 2 * num_cu();      // two workgroups per CU (launch bounds)
-    hipLaunchKernelGGL(k_assign16<false>, dim3(grid), dim3(256), A16_LDS_BYTES, (hipStream_t)stream, a);
-    DANBO_LAUNCH_RET();
+    return launch_assign16<false>(a, n, stream);
 }
 
 extern "C" int danbo_gather_assign_blend16_train(const float* rays_o, const float* rays_d, const float* z, int R, int S, int G,
@@ -633,13 +635,9 @@ extern "C" int danbo_gather_assign_blend16_train(const float* rays_o, const floa
                                                  const int32_t* count, const int32_t* first, int n, const void* packed16,
                                                  const float* b0, const float* b1, const float* w2, const float* b2, float* h,
                                                  uint32_t* ticket, void* stream) {
-    DANBO_CHECK_ARG(n >= 0 && valid_bits && h && packed16 && list && count && z && ticket && R > 0 && S > 0 && G > 0 && R % G == 0);
+    DANBO_CHECK_ARG(n >= 0 && valid_bits && h && packed16 && list && count && z && ticket && shape_ok(R, S, G));
     if (n == 0) return 0;
     A16Args a = {rays_o, rays_d, z, nullptr, R, S, G, skts, align, axis_scale, volumes, valid_bits, list, count, n,
                  reinterpret_cast<const char*>(packed16), b0, b1, w2, b2, h, nullptr, first, nullptr, ticket, a16_no_skip()};
-    DANBO_ENSURE_LDS(k_assign16<true>, A16_LDS_BYTES);
-    const int ntiles = ceil_div(n, A16_BM);
-    const int grid = ntiles < 2 * num_cu() ? ntiles : 2 * num_cu();
-    hipLaunchKernelGGL(k_assign16<true>, dim3(grid), dim3(256), A16_LDS_BYTES, (hipStream_t)stream, a);
-    DANBO_LAUNCH_RET();
+    return launch_assign16<true>(a, n, stream);
 }

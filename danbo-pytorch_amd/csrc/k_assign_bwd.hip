@@ -333,12 +333,12 @@ __global__ __launch_bounds__(AB_THREADS, 2) void k_assign_bwd(ABArgs a, int targ
         const float a1 = fmaxf(z1, 0.f);
         const float logit = half_sum32(a1 * s_w2[c]) + b2;
         const float sg = sigmoidf_(logit);
-        const float pj = sg * 1.002f - 0.001f;
+        const float pj = sigmoid_affine(sg);
         // ---- upstream
         float dp = c < FEAT ? s_dh[slot][c] * s_f[slot][0][c] : 0.f;   // neighbour 0 is the bone itself
         dp = half_sum32(dp);
         if (a.d_p != nullptr) dp += a.d_p[(size_t)s_pi[pl] * J + j];
-        float dlogit = (dp + a.c_ss * (qrow - lab)) * 1.002f * sg * (1.0f - sg);
+        float dlogit = sigmoid_affine_bwd(dp + a.c_ss * (qrow - lab), sg);
         if (!live) dlogit = 0.f;
         if (live && c == 0 && j == __builtin_ctz(bits)) lss += (lab - qrow) * (lab - qrow);   // once per row
         // ---- layer 2, 1 adjoints
@@ -482,7 +482,7 @@ using namespace danbo;
 
 extern "C" int danbo_assign_blend_bwd(const DanboAssignBwd* p, void* stream) {
     DANBO_CHECK_ARG(p && p->rays_o && p->rays_d && p->z_c && p->z_f && p->skts && p->align && p->axis_scale && p->volumes);
-    DANBO_CHECK_ARG(p->R > 0 && p->S > 0 && p->Sf > 0 && p->G > 0 && p->R % p->G == 0 && p->rows_cap > 0);
+    DANBO_CHECK_ARG(p->Sf > 0 && p->rows_cap > 0 && shape_ok(p->R, p->S, p->G));
     DANBO_CHECK_ARG(p->row_sample && p->row_ray && p->cnt && p->lists && p->cntb && p->h_rows && p->d_h && p->label_c && p->label_f);
     DANBO_CHECK_ARG(p->bits_c && p->bits_f && p->w0 && p->adj_w && p->adj && p->b0 && p->w1 && p->b1 && p->w2 && p->b2);
     DANBO_CHECK_ARG(p->g_w0 && p->g_adj_w && p->g_b0 && p->g_w1 && p->g_b1 && p->g_w2 && p->g_b2 && p->g_vol && p->g_scale && p->loss);

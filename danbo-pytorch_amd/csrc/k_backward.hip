@@ -45,15 +45,9 @@ __global__ __launch_bounds__(GB_BLOCK) void k_bone_gather_bwd(const float* __res
         const int row = tile * GB_TS + sl;
         if (row >= n) continue;
         const long m = list ? list[row] : row;
-        const int g = (int)min(m / spp, (long)G - 1);
+        const int g = pose_of_sample(m, spp, G);
         float p[3], pt[3], sk[12];
-        if (pts) { p[0] = pts[3 * m]; p[1] = pts[3 * m + 1]; p[2] = pts[3 * m + 2]; }
-        else {
-            const int r = (int)(m / S);
-            const float o[3] = {rays_o[3 * r], rays_o[3 * r + 1], rays_o[3 * r + 2]};
-            const float d[3] = {rays_d[3 * r], rays_d[3 * r + 1], rays_d[3 * r + 2]};
-            sample_point(o, d, z[m], p);
-        }
+        point_of_sample(rays_o, rays_d, z, pts, m, S, p);
         const float* src = skts + ((size_t)g * J + j) * 16;
 #pragma unroll
         for (int i = 0; i < 12; ++i) sk[i] = src[i];
@@ -126,8 +120,7 @@ extern "C" int danbo_bone_gather_bwd(const float* rays_o, const float* rays_d, c
                                       int S, int G, const float* skts, const float* align, const float* axis_scale,
                                       const float* volumes, const int32_t* list, int n, const float* d_part_feat,
                                       float* d_volumes, float* d_axis_scale, void* stream) {
-    DANBO_CHECK_ARG(R > 0 && S > 0 && G > 0 && R % G == 0 && n >= 0 && d_part_feat && d_volumes && d_axis_scale);
-    DANBO_CHECK_ARG((z == nullptr) != (pts == nullptr));
+    DANBO_CHECK_ARG(n >= 0 && d_part_feat && d_volumes && d_axis_scale && shape_ok(R, S, G) && one_of(z, pts));
     if (n == 0) return 0;
     const int ntiles = ceil_div(n, GB_TS);
     const int grid = ntiles < num_cu() * 4 ? ntiles : num_cu() * 4;

@@ -58,24 +58,19 @@ __global__ __launch_bounds__(CR_BLOCK) void k_cull_rays(const int32_t* __restric
         s_d[i] = make_float4(rays_d[3 * r], rays_d[3 * r + 1], rays_d[3 * r + 2], COARSE ? far[r] : 0.f);
         s_m[i] = make_float4(lo - slack, hi + slack, __builtin_bit_cast(float, ray_mask[r]), __builtin_bit_cast(float, r));
     }
+    // stage_bone_tables (common.hpp, pad 0) restated: the pose's transforms ride in the align loop; apart, both instantiations moved
     for (int i = tid; i < J * 16; i += CR_BLOCK) { s_align[i] = align[i]; s_skt[i] = skts[i]; }
     for (int i = tid; i < J * 4; i += CR_BLOCK) s_scale[i] = (i & 3) < 3 ? fabsf(axis_scale[(i >> 2) * 3 + (i & 3)]) : 0.f;
     __syncthreads();
 
     const float inv_S = 1.0f / (float)S;
-    auto ray_of = [&](int li) {          // li / S, exact for li < 2^22 (k_bone_cull's)
-        int q = (int)((float)li * inv_S);
-        q -= (q * S > li) ? 1 : 0;
-        q += ((q + 1) * S <= li) ? 1 : 0;
-        return q;
-    };
     const int nturns = (T + CR_PAIR - 1) / CR_PAIR;
 
     // ---- 1. depths, words, ballots
     for (int c = 0; c < nturns; ++c) {
         const int la = c * CR_PAIR + tid, lb = la + CR_BLOCK;
         const int lac = min(la, T - 1), lbc = min(lb, T - 1);            // (a tail sample repeats the last one and stores nothing)
-        const int ia = ray_of(lac), ib = ray_of(lbc);
+        const int ia = ray_of_local(lac, S, inv_S), ib = ray_of_local(lbc, S, inv_S);
         const int sa = lac - ia * S, sb = lbc - ib * S;
         const float4 oa = s_o[ia], da = s_d[ia], qa = s_m[ia];
         const float4 ob = s_o[ib], db = s_d[ib], qb = s_m[ib];
@@ -142,7 +137,7 @@ __global__ __launch_bounds__(CR_BLOCK) void k_cull_rays(const int32_t* __restric
             const unsigned long long ball = s_ball[k];
             if ((ball >> lane) & 1ull) {             // (set only for local samples < T)
                 const int li = c * CR_PAIR + h * CR_BLOCK + tid;
-                const int i = ray_of(li);
+                const int i = ray_of_local(li, S, inv_S);
                 const int r = __builtin_bit_cast(int, s_m[i].w);
                 list[base + s_off[k] + (int)__popcll(ball & ((1ull << lane) - 1ull))] = (int32_t)(r * S + (li - i * S));
             }

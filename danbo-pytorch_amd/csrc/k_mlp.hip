@@ -596,7 +596,7 @@ extern "C" int danbo_view_consts(const float* rays_d, const float* skts, int R, 
                                   const float* rgb_w, const float* rgb_b, const float* empty_consts, int rgb_order,
                                   const float* code_table, const int32_t* ray_list, const int32_t* ray_count, float* cview,
                                   float* raw_empty, void* stream) {
-    DANBO_CHECK_ARG(R > 0 && G > 0 && R % G == 0 && L_view >= 0 && Cf >= 0);
+    DANBO_CHECK_ARG(L_view >= 0 && Cf >= 0 && poses_ok(R, G));
     DANBO_CHECK_ARG((ray_list == nullptr) == (ray_count == nullptr));
     DANBO_CHECK_ARG(Cf == 0 || (mean_code != nullptr && (cam_idx == nullptr || framecodes != nullptr)));
     DANBO_CHECK_ARG((empty_consts == nullptr) == (raw_empty == nullptr));

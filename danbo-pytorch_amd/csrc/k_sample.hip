@@ -236,20 +236,6 @@ __global__ __launch_bounds__(256) void k_coarse_samples(const float* __restrict_
     }
 }
 
-// sample point m: either o + d*z (two roundings, core/raycasters.py:463) or read from pts
-__device__ __forceinline__ void load_point(const float* __restrict__ rays_o, const float* __restrict__ rays_d,
-                                           const float* __restrict__ z, const float* __restrict__ pts, long m, int S,
-                                           float* p) {
-    if (pts != nullptr) {
-        p[0] = pts[3 * m]; p[1] = pts[3 * m + 1]; p[2] = pts[3 * m + 2];
-    } else {
-        const int r = (int)(m / S);
-        const float o[3] = {rays_o[3 * r], rays_o[3 * r + 1], rays_o[3 * r + 2]};
-        const float d[3] = {rays_d[3 * r], rays_d[3 * r + 1], rays_d[3 * r + 2]};
-        sample_point(o, d, z[m], p);
-    }
-}
-
 // ======================================================================================
 // K1a: transform + cull
 // ======================================================================================
@@ -308,8 +294,7 @@ __global__ __launch_bounds__(256) void k_ray_bone_mask(const float* __restrict__
     const float o[3] = {rays_o[3 * r], rays_o[3 * r + 1], rays_o[3 * r + 2]};
     const float d[3] = {rays_d[3 * r], rays_d[3 * r + 1], rays_d[3 * r + 2]};
     const float zl = t_lo[r], zh = t_hi[r];
-    for (int i = threadIdx.x; i < J * 16; i += 256) s_align[i] = align[i];
-    for (int i = threadIdx.x; i < J * 4; i += 256) s_scale[i] = (i & 3) < 3 ? fabsf(axis_scale[(i >> 2) * 3 + (i & 3)]) : 0.f;
+    stage_bone_tables<256>(align, axis_scale, s_align, s_scale, 0.f);
     if (POSES_IN_LDS)
         for (int i = threadIdx.x; i < (g1 - g0 + 1) * J * 16; i += 256) s_skt[i] = skts[(size_t)g0 * J * 16 + i];
     __syncthreads();
@@ -377,8 +362,7 @@ __global__ __launch_bounds__(CULL_BLOCK) void k_bone_cull(const float* __restric
     const long spp = (long)(R / G) * S;  // samples per pose
     const long base = (long)blockIdx.x * (CULL_BLOCK * CULL_SPT);
     const long last = min(base + CULL_BLOCK * CULL_SPT, M) - 1;
-    const int g0 = (int)min(base / spp, (long)G - 1);
-    const int g1 = (int)min(last / spp, (long)G - 1);
+    const int g0 = pose_of_sample(base, spp, G), g1 = pose_of_sample(last, spp, G);
 
     const int lane = threadIdx.x & 63;
     // 32-bit bookkeeping of the workgroup's 1024 samples: sample k * 256 + tid of the workgroup is ray r_first + li / S with
@@ -388,12 +372,6 @@ __global__ __launch_bounds__(CULL_BLOCK) void k_bone_cull(const float* __restric
     const int off0 = (int)(base - (long)r_first * S);
     const int rays_per_pose = R / G;
     const float inv_S = 1.0f / (float)S;
-    auto ray_of = [&](int li) {          // r_first + li / S, exact for li < 2^22
-        int q = (int)((float)li * inv_S);
-        q -= (q * S > li) ? 1 : 0;
-        q += ((q + 1) * S <= li) ? 1 : 0;
-        return q;
-    };
     auto pose_of = [&](int r) { return G == 1 ? 0 : min(r / rays_per_pose, G - 1); };
     // ---- ray-level rejection (z mode): a bone whose slightly inflated box the ray's sampled segment misses
     // cannot contain any of the ray's samples, so whole wavefronts skip it.  Conservative (margins far above
@@ -417,7 +395,7 @@ __global__ __launch_bounds__(CULL_BLOCK) void k_bone_cull(const float* __restric
         for (int k = 0; k < CULL_SPT; ++k) {
             pre[k] = 0u;
             if (base + k * CULL_BLOCK + threadIdx.x < M) {
-                const int r = r_first + ray_of(off0 + k * CULL_BLOCK + threadIdx.x);
+                const int r = r_first + ray_of_local(off0 + k * CULL_BLOCK + threadIdx.x, S, inv_S);
                 const float lo = t_lo[r], hi = t_hi[r];
                 const float slack = mask_slack(lo, hi);
                 const bool inside = zreg[k] >= lo - slack && zreg[k] <= hi + slack;
@@ -433,8 +411,7 @@ __global__ __launch_bounds__(CULL_BLOCK) void k_bone_cull(const float* __restric
             return;
         }
     }
-    for (int i = threadIdx.x; i < J * 16; i += CULL_BLOCK) s_align[i] = align[i];
-    for (int i = threadIdx.x; i < J * 4; i += CULL_BLOCK) s_scale[i] = (i & 3) < 3 ? fabsf(axis_scale[(i >> 2) * 3 + (i & 3)]) : 0.f;
+    stage_bone_tables<CULL_BLOCK>(align, axis_scale, s_align, s_scale, 0.f);
     const int npose = g1 - g0 + 1;  // <= np_lds by construction of the launch
     for (int i = threadIdx.x; i < npose * J * 16; i += CULL_BLOCK) s_skt[i] = skts[(size_t)g0 * J * 16 + i];
     __syncthreads();
@@ -452,7 +429,7 @@ __global__ __launch_bounds__(CULL_BLOCK) void k_bone_cull(const float* __restric
 #pragma unroll
         for (int k = 0; k < CULL_SPT; ++k) {
             if (base + k * CULL_BLOCK + threadIdx.x < M) {
-                const int i = ray_of(off0 + k * CULL_BLOCK + threadIdx.x);
+                const int i = ray_of_local(off0 + k * CULL_BLOCK + threadIdx.x, S, inv_S);
                 const int oz = ordered(zreg[k]);
                 atomicMin(&s_lo[i], oz);
                 atomicMax(&s_hi[i], oz);
@@ -489,7 +466,7 @@ __global__ __launch_bounds__(CULL_BLOCK) void k_bone_cull(const float* __restric
         const long mac = min(ma, M - 1), mbc = min(mb, M - 1);
         // (clamped tail samples repeat the last sample: local index of the clamp)
         const int lia = (int)(mac - base) + off0, lib = (int)(mbc - base) + off0;
-        const int ra = r_first + ray_of(lia), rb = r_first + ray_of(lib);
+        const int ra = r_first + ray_of_local(lia, S, inv_S), rb = r_first + ray_of_local(lib, S, inv_S);
         float pa[3], pb[3];
         if (pts != nullptr) {
             pa[0] = pts[3 * mac]; pa[1] = pts[3 * mac + 1]; pa[2] = pts[3 * mac + 2];
@@ -593,14 +570,13 @@ __global__ __launch_bounds__(GATHER_BLOCK) void k_bone_gather(const float* __res
     const int tid = threadIdx.x;
     const int sl = tid / J, j = tid % J;
 
-    for (int i = tid; i < J * 16; i += GATHER_BLOCK) s_align[i] = align[i];
-    for (int i = tid; i < J * 4; i += GATHER_BLOCK) s_scale[i] = (i & 3) < 3 ? fabsf(axis_scale[(i >> 2) * 3 + (i & 3)]) : 1.f;
+    stage_bone_tables<GATHER_BLOCK>(align, axis_scale, s_align, s_scale, 1.f);
     int g_lds = -1;
 
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int row0 = tile * GATHER_TS;
         const int first = list ? list[row0] : row0;
-        const int g_tile = (int)min((long)first / spp, (long)G - 1);
+        const int g_tile = pose_of_sample(first, spp, G);
         __syncthreads();  // previous tile's s_out fully stored, s_vol no longer read
         if (g_tile != g_lds) {
             const float4* src = reinterpret_cast<const float4*>(volumes + (size_t)g_tile * J * VOL);
@@ -614,9 +590,9 @@ __global__ __launch_bounds__(GATHER_BLOCK) void k_bone_gather(const float* __res
         float* o_ = s_out + (sl * J + j) * FEAT;
         if (row < n) {
             const long m = list ? list[row] : row;
-            const int g = (int)min(m / spp, (long)G - 1);
+            const int g = pose_of_sample(m, spp, G);
             float p[3], pt[3], f[FEAT];
-            load_point(rays_o, rays_d, z, pts, m, S, p);
+            point_of_sample(rays_o, rays_d, z, pts, m, S, p);
             if (g == g_lds) {
                 bone_local(s_skt + 16 * j, s_align + 16 * j, p, pt);
                 gather_bone_features(s_vol + j * VOL, pt, s_scale + 4 * j, f);
@@ -1238,7 +1214,7 @@ static unsigned ray_scatter(int R) {
 extern "C" int danbo_near_far_cylinder(const float* rays_o, const float* rays_d, const float* cyl, int R, int G,
                                         float near0, float far0, const float* near_in, const float* far_in, int chunk,
                                         float* scratch, float* near_out, float* far_out, void* stream) {
-    DANBO_CHECK_ARG(R > 0 && G > 0 && R % G == 0 && chunk > 0 && scratch != nullptr);
+    DANBO_CHECK_ARG(chunk > 0 && scratch != nullptr && poses_ok(R, G));
     hipStream_t st = (hipStream_t)stream;
     const int nchunk = ceil_div(R, chunk);
     if (chunk <= CYL_FUSED_MAX) {       // (the scratch stays untouched)
@@ -1258,7 +1234,7 @@ extern "C" int danbo_near_far_cylinder(const float* rays_o, const float* rays_d,
 extern "C" int danbo_near_far_boxes(const float* rays_o, const float* rays_d, const float* skts, const float* align,
                                      const float* axis_scale, int R, int G, float* near_io, float* far_io,
                                      void* stream) {
-    DANBO_CHECK_ARG(R > 0 && G > 0 && R % G == 0);
+    DANBO_CHECK_ARG(poses_ok(R, G));
     hipLaunchKernelGGL(k_box_bounds, dim3(stream_grid((long)R * 32, 256)), dim3(256), 0, (hipStream_t)stream, rays_o, rays_d, skts,
                        align, axis_scale, R, G, near_io, far_io);
     DANBO_LAUNCH_RET();
@@ -1280,9 +1256,9 @@ extern "C" int danbo_bone_cull(const float* rays_o, const float* rays_d, const f
                                 const float* skts, const float* align, const float* axis_scale, const uint32_t* ray_mask,
                                 const float* t_lo, const float* t_hi, uint32_t* ray_flat, uint32_t* valid_bits, int32_t* list,
                                 int32_t* count, void* stream) {
-    DANBO_CHECK_ARG(R > 0 && S > 0 && G > 0 && R % G == 0);
+    DANBO_CHECK_ARG(shape_ok(R, S, G));
     DANBO_CHECK_ARG((list == nullptr) == (count == nullptr));
-    DANBO_CHECK_ARG((z == nullptr) != (pts == nullptr));
+    DANBO_CHECK_ARG(one_of(z, pts));
     DANBO_CHECK_ARG(ray_mask == nullptr || (z != nullptr && t_lo != nullptr && t_hi != nullptr));
     DANBO_CHECK_ARG(ray_flat == nullptr || ray_mask != nullptr);
     const long M = (long)R * S;
@@ -1301,8 +1277,7 @@ extern "C" int danbo_bone_cull(const float* rays_o, const float* rays_d, const f
 extern "C" int danbo_ray_bone_mask(const float* rays_o, const float* rays_d, const float* t_lo, const float* t_hi, int R, int G,
                                     const float* skts, const float* align, const float* axis_scale, uint32_t* ray_mask,
                                     uint32_t* ray_flat, void* stream) {
-    DANBO_CHECK_ARG(rays_o && rays_d && t_lo && t_hi && skts && align && axis_scale && ray_mask);
-    DANBO_CHECK_ARG(R > 0 && G > 0 && R % G == 0);
+    DANBO_CHECK_ARG(rays_o && rays_d && t_lo && t_hi && skts && align && axis_scale && ray_mask && poses_ok(R, G));
     const long np = 256 / (R / G) + 2 < G ? 256 / (R / G) + 2 : G;     // poses a workgroup's 256 rays can span
     const bool in_lds = np <= 8;
     const size_t lds = sizeof(float) * (J * 16 + J * 4 + (in_lds ? np * J * 16 : 0));
@@ -1319,8 +1294,7 @@ extern "C" int danbo_bone_gather_fwd(const float* rays_o, const float* rays_d, c
                                       const float* skts, const float* align, const float* axis_scale,
                                       const float* volumes, const int32_t* list, const int32_t* count, int n,
                                       float* part_feat, void* stream) {
-    DANBO_CHECK_ARG(R > 0 && S > 0 && G > 0 && R % G == 0 && n >= 0);
-    DANBO_CHECK_ARG((z == nullptr) != (pts == nullptr));
+    DANBO_CHECK_ARG(n >= 0 && shape_ok(R, S, G) && one_of(z, pts));
     if (n == 0) return 0;
     const int ntiles = ceil_div(n, GATHER_TS);
     const int grid = ntiles < num_cu() * 3 ? ntiles : num_cu() * 3;

@@ -394,7 +394,7 @@ static inline int few_grid(long items, int block) {
 extern "C" int danbo_train_view_inputs(const float* rays_d, const float* skts, int R, int G, int ray_mode, int normalise, int L_view,
                                        const float* codes, int n_codes, int Cf, const int64_t* cam_idx, float* vin, int ldv,
                                        void* stream) {
-    DANBO_CHECK_ARG(rays_d && vin && R > 0 && G > 0 && R % G == 0 && L_view >= 0 && ldv % 4 == 0);
+    DANBO_CHECK_ARG(rays_d && vin && L_view >= 0 && ldv % 4 == 0 && poses_ok(R, G));
     DANBO_CHECK_ARG(ldv >= 3 * (1 + 2 * L_view) + (codes ? Cf : 0) && (ray_mode == 0 || skts));
     hipLaunchKernelGGL(k_train_view_inputs, dim3(stream_grid((long)R * ldv, 256)), dim3(256), 0, (hipStream_t)stream, rays_d, skts, R, G,
                        ray_mode, normalise, L_view, codes, n_codes, Cf, cam_idx, vin, ldv);

@@ -83,6 +83,21 @@ DANBO_HD void sample_point(const float* o, const float* d, float z, float* p) {
     p[2] = add_rn(o[2], mul_rn(d[2], z));
 }
 
+// pose of sample m of an [R, S] batch that holds G poses, spp = (R / G) * S samples each (clamped like the rays' r / (R / G))
+DANBO_HD int pose_of_sample(long m, long spp, int G) { return (int)(m / spp < (long)G - 1 ? m / spp : (long)G - 1); }
+// the point of sample m: pts[m] where the caller brings points, o + d z of ray m / S otherwise
+DANBO_HD void point_of_sample(const float* __restrict__ rays_o, const float* __restrict__ rays_d, const float* __restrict__ z,
+                              const float* __restrict__ pts, long m, int S, float* p) {
+    if (pts != nullptr) {
+        p[0] = pts[3 * m]; p[1] = pts[3 * m + 1]; p[2] = pts[3 * m + 2];
+    } else {
+        const int r = (int)(m / S);
+        const float o[3] = {rays_o[3 * r], rays_o[3 * r + 1], rays_o[3 * r + 2]};
+        const float d[3] = {rays_d[3 * r], rays_d[3 * r + 1], rays_d[3 * r + 2]};
+        sample_point(o, d, z[m], p);
+    }
+}
+
 // (m0*x + m1*y) + m2*z for the three rows of a row-major 4x4: the rotation alone, what a DIRECTION takes (torch.matmul's
 // sequential-k order).  q must not alias d.
 DANBO_HD void rotate_unfused(const float* M, const float* d, float* q) {
@@ -166,10 +181,12 @@ DANBO_HD void gather_bone_features(VolPtr vol, const float* pt, const float* abs
 
 DANBO_HD float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
-// colour of a sample (core/networks/nerf.py:281-347): sigmoid(logit) * 1.002 - 0.001, two roundings.  rgb_affine: of the sigmoid
-// itself, for the code that keeps it (the composite's backward)
-DANBO_HD float rgb_affine(float s) { return sub_rn(mul_rn(s, 1.002f), 0.001f); }
-DANBO_HD float rgb_of_logit(float x) { return rgb_affine(sigmoidf_(x)); }
+// What the reference makes of a sigmoid s, a sample's colour (core/networks/nerf.py:281-347) and a bone's assignment probability
+// alike: s * 1.002 - 0.001, two roundings.  _bwd: the gradient `up` of that taken to the logit, ((up * 1.002) * s) * (1 - s)
+constexpr float SIGMOID_GAIN = 1.002f, SIGMOID_SHIFT = 0.001f;
+DANBO_HD float sigmoid_affine(float s) { return sub_rn(mul_rn(s, SIGMOID_GAIN), SIGMOID_SHIFT); }
+DANBO_HD float sigmoid_affine_bwd(float up, float s) { return up * SIGMOID_GAIN * s * (1.0f - s); }
+DANBO_HD float rgb_of_logit(float x) { return sigmoid_affine(sigmoidf_(x)); }
 // disparity of a ray from its weighted depth and accumulated weight: 1 / max(1e-10, depth / (acc + 1e-10)), 0 where
 // torch.isclose(acc, 0): |acc| <= 1e-8 + 1e-5 * 0
 DANBO_HD float disp_of(float depth, float acc) {

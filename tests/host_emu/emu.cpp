@@ -18,10 +18,11 @@ void emu_cull_gather(const float* rays_o, const float* rays_d, const float* z, i
                      float* part_feat) {
     float sc[J * 3];
     for (int i = 0; i < J * 3; ++i) sc[i] = fabsf(axis_scale[i]);
+    const long spp = (long)(R / G) * S;
     for (long m = 0; m < (long)R * S; ++m) {
-        const int r = (int)(m / S), g = r / (R / G);
+        const int g = pose_of_sample(m, spp, G);
         float p[3];
-        sample_point(rays_o + 3 * r, rays_d + 3 * r, z[m], p);
+        point_of_sample(rays_o, rays_d, z, nullptr, m, S, p);
         uint32_t b = 0;
         for (int j = 0; j < J; ++j) {
             float pt[3];

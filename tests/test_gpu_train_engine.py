@@ -21,14 +21,10 @@ def P(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
-def stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def test_grouped_weight_gradients_match_torch():
     """danbo_dw16 on row-major operands: a two-input layer (the skip layer's shape), a 3-wide and a 1-wide layer in ONE launch,
     gradient magnitudes ~1e-7 (power-of-two pre-scale from the recorded max), device-side row count below the capacity"""
-    from core import _hip
+    from core import _hip, hip_ops as ops
     g = torch.Generator(device="cpu").manual_seed(0)
     M, live = 1000, 700
     pe = torch.zeros(M, 196, device=DEV)
@@ -45,15 +41,13 @@ def test_grouped_weight_gradients_match_torch():
     gw3, gb3 = torch.full((3, 128), 7., device=DEV), torch.full((3,), 7., device=DEV)
     gw1, gb1 = torch.full((1, 256), 7., device=DEV), torch.full((1,), 7., device=DEV)
     mx3 = d3.abs().max().reshape(1).clone()
-    L = (_hip.DanboDwLayer * 3)(
+    L = [
         _hip.DanboDwLayer(dy=P(dz), x1=P(pe), x2=P(y4), dy_maxabs=P(mx_in), gw=P(gw5), gb=P(gb5), ldy=256, ld1=196, ld2=256,
                           N=256, K1=195, K2=256),
         _hip.DanboDwLayer(dy=P(d3), x1=P(hv), dy_maxabs=P(mx3), gw=P(gw3), gb=P(gb3), ldy=4, ld1=128, N=3, K1=128),
-        _hip.DanboDwLayer(dy=P(d1), x1=P(y4), dy_maxabs=P(mx3), gw=P(gw1), gb=P(gb1), ldy=4, ld1=256, N=1, K1=256))
-    slices = 5
-    scratch = torch.empty(_hip.lib().danbo_dw16_scratch_floats(L, 3, slices), device=DEV)
+        _hip.DanboDwLayer(dy=P(d1), x1=P(y4), dy_maxabs=P(mx3), gw=P(gw1), gb=P(gb1), ldy=4, ld1=256, N=1, K1=256)]
     n_live = torch.tensor([live - 13], dtype=torch.int32, device=DEV)       # device-side row count below the capacity
-    _hip.check(_hip.lib().danbo_dw16(L, 3, live, P(n_live), slices, P(scratch), stream()), "dw16")
+    ops.dw16(L, live, DEV, n_live, slices=5)
     rows = slice(0, live - 13)
     for gw, gb, dy, x in ((gw5, gb5, dz[rows], torch.cat([pe[rows, :195], y4[rows]], 1)), (gw3, gb3, d3[rows, :3], hv[rows]),
                           (gw1, gb1, d1[rows, :1], y4[rows])):
@@ -544,13 +538,11 @@ def test_weight_gradients_from_fragment_order_operands_and_split_layers():
     gb2 = torch.zeros(256, device=DEV)
     D = _hip.DanboDwLayer
     common = dict(dy_maxabs=P(mx), gw2=None, gb2=None, ldy=256, ld2=0, N=256, K2=0, split_n=0, x2=None)
-    L = (D * 3)(D(dy=P(fdy), x1=P(xa), gw=P(gw), gb=P(gb), ld1=196, K1=195, frag=1, gw_ld=451, gw_col0=0, **common),
-                D(dy=P(fdy), x1=P(fxb), gw=P(gw), gb=None, ld1=256, K1=256, frag=3, gw_ld=451, gw_col0=195, **common),
-                D(dy=P(dy), x1=P(fxb), gw=P(gw2), gb=P(gb2), ld1=256, K1=256, frag=2, gw_ld=0, gw_col0=0, **common))
-    slices = 7
-    scratch = torch.empty(_hip.lib().danbo_dw16_scratch_floats(L, 3, slices), device=DEV)
+    L = [D(dy=P(fdy), x1=P(xa), gw=P(gw), gb=P(gb), ld1=196, K1=195, frag=1, gw_ld=451, gw_col0=0, **common),
+         D(dy=P(fdy), x1=P(fxb), gw=P(gw), gb=None, ld1=256, K1=256, frag=3, gw_ld=451, gw_col0=195, **common),
+         D(dy=P(dy), x1=P(fxb), gw=P(gw2), gb=P(gb2), ld1=256, K1=256, frag=2, gw_ld=0, gw_col0=0, **common)]
     n_live = torch.tensor([M], dtype=torch.int32, device=DEV)
-    _hip.check(_hip.lib().danbo_dw16(L, 3, M + 50, P(n_live), slices, P(scratch), stream()), "dw16")
+    ops.dw16(L, M + 50, DEV, n_live, slices=7)
     ref = (dy.double().t() @ torch.cat([xa[:, :195], xb], 1).double()).float()
     ref_b = dy.double().sum(0).float()
     assert float((gw - ref).abs().max()) <= 2e-5 * float(ref.abs().max())

@@ -111,7 +111,8 @@ def test_composite_backward_matches_torch_autograd():
 
 
 def test_gather_backward_against_finite_differences():
-    from core import hip_ops as ops, train_path
+    from core import custom_ops  # noqa: F401  (registers torch.ops.danbo.bone_gather)
+    from core import hip_ops as ops
     from core.utils import synthetic as syn
     g = golden("danbo_stages")
     rb = g["ray_batch"]
@@ -123,12 +124,30 @@ def test_gather_backward_against_finite_differences():
     bits, lst, cnt = ops.bone_cull(geo, True)
     rows = torch.sort(lst[: int(cnt.item())]).values.contiguous()
     w = T(np.random.default_rng(0).normal(size=(rows.shape[0], 24, 15)))
-    pf = train_path.GatherFn.apply(vols, sc, geo, rows)
+    pts = (geo.rays_o[:, None, :] + geo.rays_d[:, None, :] * geo.z[..., None]).contiguous()     # o + d z, two roundings: the kernels' points
+    gather = lambda v, s: torch.ops.danbo.bone_gather(v, s, pts, geo.skts, geo.align, rows)     # noqa: E731
+    pf = gather(vols, sc)
     (pf * w).sum().backward()
     # d volumes: the forward is linear in the volumes -> exact directional check
     dv = T(np.random.default_rng(1).normal(size=tuple(vols.shape)))
-    lin = (train_path.GatherFn.apply(dv, sc.detach(), geo, rows) * w).sum()
+    lin = (gather(dv, sc.detach()) * w).sum()
     assert abs(float((vols.grad * dv).sum()) - float(lin)) <= 1e-4 * abs(float(lin))
+    # The C entry point in depth mode (rays + z: the package itself passes points): the kernel forms the same points bit for bit, so
+    # every term of d volumes is the same float and only the order of the fp32 atomic additions differs from the run above.  A term
+    # of d volumes has the sign of its upstream value (the interpolation weights and the window are >= 0), so the same call on |w|
+    # gives sum |terms| per entry, and two orders of at most n additions differ by at most 2 n 2^-24 of it.
+    vols_c = vols.detach().contiguous()
+
+    def depth_mode(up):
+        d_vol, d_sc = torch.zeros(tuple(vols.shape), device=DEV), torch.zeros(tuple(sc.shape), device=DEV)
+        ops._call("danbo_bone_gather_bwd", *geo.head(), ops._p(vols_c), ops._p(rows), rows.shape[0], ops._p(up), ops._p(d_vol),
+                  ops._p(d_sc), ops._stream())
+        return d_vol
+    bound = 2 * rows.shape[0] * 2.0 ** -24 * depth_mode(w.abs()) * (1 + 1e-3)
+    diff = (depth_mode(w) - vols.grad).abs()
+    print("depth mode against point mode: max |difference| of d volumes", float(diff.max()), "of", float(vols.grad.abs().max()),
+          "; n =", rows.shape[0], ", entries above their bound:", int((diff > bound).sum()))
+    assert bool((diff <= bound).all()) and float(vols.grad.abs().max()) > 0
     # d axis_scale: central differences on a few entries (window detached => freeze it via small eps only)
     base = sc.detach().clone()
     for (j, k) in [(1, 0), (4, 2), (9, 1), (16, 2)]:
@@ -137,7 +156,7 @@ def test_gather_backward_against_finite_differences():
         for sgn in (+1, -1):
             s2 = base.clone()
             s2[j, k] += sgn * eps
-            vals.append(train_path.GatherFn.apply(vols.detach(), s2, geo, rows))
+            vals.append(gather(vols.detach(), s2))
         # remove the (detached) window's own dependence on the scale: divide it out
         fd = float((((vals[0] - vals[1]) / (2 * eps)) * w).sum())
         an = float(sc.grad[j, k])

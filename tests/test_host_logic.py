@@ -418,6 +418,34 @@ def test_dw16_isa_leaves_the_producers_load_registers_alone():
     assert "vmcnt(12)" in waits, waits
 
 
+def test_compiled_in_smpl_tree_is_the_skeletons():
+    """Every table of the SMPL tree that a kernel has compiled in is SMPLSkeleton.joint_trees, the tree
+    hip_ops.check_smpl_adjacency holds a checkpoint's graph against, so the copies cannot disagree with it or with each other:
+    k_assign.hip's c_parent [24] and c_nbr [24][4] (a bone's parent, then its children by index, -1 padded), k_assign16.hip's
+    a16_deg [24] and a16_nb [24][5] (the bone itself first).  Read out of the emitted constant data of the two translation units."""
+    from core.utils.skeleton_utils import SMPLSkeleton, get_children_joints
+
+    def table(text, symbol, dtype):
+        block = text[text.index(symbol + ":\n"):]
+        block = block[:block.index(".size")]
+        if dtype is np.int8:
+            raw = b"".join(t.encode("latin-1").decode("unicode_escape").encode("latin-1") for t in re.findall(r'\.ascii\s+"(.*)"', block))
+            return np.frombuffer(raw, np.int8)
+        return np.array([int(v) for v in re.findall(r"\.long\s+(\d+)", block)], np.uint32).astype(np.int32)
+
+    tree = [int(p) for p in SMPLSkeleton.joint_trees]
+    children = get_children_joints()
+    want = [([tree[j]] if tree[j] != j else []) + [c for c in children[j] if c != j] for j in range(24)]
+    text = isa.device_asm("k_assign")
+    assert table(text, "_ZN5danbo8c_parentE", np.int8).tolist() == tree
+    assert table(text, "_ZN5danbo5c_nbrE", np.int8).reshape(24, 4).tolist() == [w + [-1] * (4 - len(w)) for w in want]
+    text = isa.device_asm("k_assign16")
+    assert table(text, "__const._ZN5danbo7a16_degEi.d", np.int32).tolist() == [len(w) for w in want]
+    assert table(text, "__const._ZN5danbo6a16_nbEii.nb", np.int32).reshape(24, 5).tolist() == [[j] + w + [-1] * (4 - len(w))
+                                                                                                 for j, w in enumerate(want)]
+    assert sum(len(w) for w in want) == 2 * 23 and 24 + sum(len(w) for w in want) == 70      # 23 edges, 70 adjacency non-zeros
+
+
 def test_ring_kernels_do_not_spill():
     """The kernels that stream weights through an LDS ring with hand-counted vmcnt waits must not spill: a scratch access is a
     VMEM operation the compiler waits for with vmcnt(0), which drains the ring (k_pe_mlp16 with 196 B of spills moved 10x the HBM

@@ -1,4 +1,6 @@
-"""danbo_dw16 on the training step's layer mix at M rows: trunk operands row-major against fragment order (dev tool)
+"""danbo_dw16 on the training step's layer mix at M rows: trunk operands row-major against fragment order (dev tool).  Timed is
+hip_ops.dw16, the launch as the package issues it: with its scratch query and allocation (a few microseconds of host work that
+the numbers recorded with the bare C call do not hold).
     python tools/micro_dw16.py [rows] [slices] [--trunk-only]"""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -40,10 +42,7 @@ for mode in ("rows", "frag"):
     if not trunk_only:
         Ls += [layer(dz[7], 256, 256, y[7], 256, 256), layer(draw, 4, 1, y[7], 256, 256), layer(dpre, 128, 128, fa, 260, 256, vinr, 156, 155),
                layer(draw, 4, 3, hv, 128, 128)]
-    L = (D * len(Ls))(*Ls)
-    scratch = torch.empty(_hip.lib().danbo_dw16_scratch_floats(L, len(Ls), slices), device=dev)
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    run = lambda: _hip.check(_hip.lib().danbo_dw16(L, len(Ls), M, None, slices, P(scratch), st), "dw16")
+    run = lambda: ops.dw16(Ls, M, dev, slices=slices)
     run(); torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
