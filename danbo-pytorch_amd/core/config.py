@@ -47,6 +47,9 @@ _FLAGS = [
     ("syn_poses", int, 8), ("syn_cams", int, 4), ("syn_res", int, 64), ("syn_seed", int, 0), ("syn_rest_scale", float, 0.48),
     # validation frames stay on the device and are scored there (evaluation_helpers.evaluate_metric_device)
     ("eval_device", bool, False),
+    # the reference's batch semantics (core/load_data.py sample_batch): targets composited over the background outside the mask,
+    # that background random; and the training tables resident on the GPU, every batch gathered there (danbo_batch_gather)
+    ("mask_image", bool, False), ("perturb_bg", bool, False), ("device_data", bool, False),
 ]
 
 

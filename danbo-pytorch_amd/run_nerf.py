@@ -7,7 +7,9 @@ Same flags, log directory (`args.txt`, `config.txt`, `NNNNNN.tar` checkpoints in
 reference; the renderer underneath is the HIP path.  One process drives one GPU: under `torch.distributed.run` every rank takes
 whole images of each batch (core/load_data.py) and the flat gradient is all-reduced once per step (core/trainer.py) -- the
 reference's nn.DataParallel replicas are gone.  Data: `--dataset_type synthetic` (default; seeded poses, teacher-rendered
-images) or `npz`; TensorBoard / video writers are not in this image, scalars go to stdout and `scalars.jsonl`.
+images) or `npz`; `--mask_image` / `--perturb_bg` as in the reference's loader; `--device_data` keeps the image and pose tables on
+the GPU and gathers every batch there (core/load_data.py).  TensorBoard / video writers are not in this image, scalars go to stdout
+and `scalars.jsonl`.
 """
 import json
 import os

@@ -204,7 +204,7 @@ def load_nerf(args, nerf_args, device):
 def get_render_dataset(args, nerf_args, device):
     if args.dataset == 'npz':
         d = np.load(args.entry)
-        opt = {k: d[k] for k in ('cam_idxs', 'centers') if k in d}
+        opt = {k: d[k] for k in ('cam_idxs', 'centers', 'sampling_masks') if k in d}
         return PoseImageDataset(*[d[k] for k in PoseImageDataset.KEYS], ext_scale=nerf_args.ext_scale, **opt)
     if args.dataset != 'synthetic':
         raise NotImplementedError(f"dataset '{args.dataset}': HDF5 catalogs are not readable here; export to .npz")
