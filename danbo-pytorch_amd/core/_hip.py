@@ -14,7 +14,7 @@ The header is $DANBO_HIP_HEADER, else danbo_hip.h beside the library, else inclu
 RESTYPES, STRUCTS and C are the statement of danbo_hip.h alone.  The entry points of a later feature stand in a header of their own
 beside it (a satellite), bound the same way and reached as `header("danbo_x.h").signatures / .restypes / .C / .path`: a satellite
 declares no struct, and no function or constant that an earlier header declares.  A new header is named in HEADERS, nowhere else.
-A header outside that pinned set (danbo_batch.h) is bound by the module that uses it: `bind_headers([HEADER_PATH, <path beside
+A header outside that pinned set (danbo_batch.h, danbo_grid_cc.h) is bound by the module that uses it: `bind_headers([HEADER_PATH, <path beside
 it>])[1]` gives the same parser and the same satellite rule, and the user sets argtypes / restype on `lib()`'s handle at first use.
 `lib()` refuses a library whose danbo_abi_version() is not the header's DANBO_ABI_VERSION (a stale build).
 

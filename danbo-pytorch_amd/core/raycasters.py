@@ -17,6 +17,7 @@ import torch.nn.functional as F
 
 from . import hip_ops as ops
 from .encoders import get_pe_embedder, get_pts_embedder
+from .grid_components import grid_components, keep_components
 from .render_engine import DanboEngine, RenderEngine
 from .networks import create_nerf
 from .utils.evaluation_helpers import to8b
@@ -437,7 +438,8 @@ class RayCaster(nn.Module):
 
     @torch.no_grad()
     def render_mesh_surface(self, kps, skts, bones, threshold=10., res=64, return_density=False, normals=False, colors=False,
-                            cams=None, radius=1.0, netchunk=1024 * 64, **kwargs):
+                            cams=None, radius=1.0, netchunk=1024 * 64, keep_largest=False, min_component=0, return_components=False,
+                            **kwargs):
         """The density grid of render_mesh_density and its isosurface at `threshold`, as the reference's render_mesh makes it
         (run_render.py:1278-1280): marching cubes on np.maximum(raw, 0), vertices / res - .5 per axis of the returned (x-y swapped)
         array.  The grid stays on the device and is read through its transposed view.
@@ -446,9 +448,21 @@ class RayCaster(nn.Module):
         fine network when there is one, as for the density; cams: the pose's frame-code index, where the network has frame codes).
         Entry (i, j, k) of the swapped array lies at root + (t[i], t[j], t[k]), t = linspace(-radius, radius, res + 1), so the
         vertex v in [-0.5, 0.5]^3 lies at root + 2 radius v and an index-space normal is the world-space one.
+        keep_largest / min_component (a number of grid points): the floaters go before the extraction -- the grid's 6-connected
+        components at `threshold` are labelled on the device (core/grid_components.py) and the ones that are not the largest, or
+        are smaller than min_component, are set to 0 in a filtered copy of the grid, laid out like the grid itself; vertices,
+        faces, normals and colours are the filtered grid's, and return_density returns it.  Every vertex on a kept component is, bit
+        for bit, a vertex of the unfiltered surface.  With both left off nothing is labelled and nothing changes.
+        return_components: also (stats [4], kept [2]) int32 device tensors of grid_components / keep_components, or None unfiltered.
         -> verts [V,3] float32, faces [T,3] int32 [, normals [V,3] float32] [, colors [V,3] uint8] (device tensors) [, the raw
-        density grid]"""
+        density grid] [, (stats, kept)]"""
         dens = self.render_mesh_density(kps, skts, bones, res=res, radius=radius, netchunk=netchunk, **kwargs)
+        components = None
+        if keep_largest or min_component:
+            labels, sizes, stats = grid_components(dens, float(threshold), floor=0.)
+            dens, kept = keep_components(dens, float(threshold), 0., labels, sizes, stats, keep_largest=bool(keep_largest),
+                                         min_points=int(min_component), fill=0.)
+            components = (stats, kept)
         mesh = ops.marching_cubes(dens, float(threshold), floor=0., scale=1. / res, offset=(-.5, -.5, -.5), normals=normals or colors)
         out = list(mesh[:3] if normals else mesh[:2])
         if colors:
@@ -459,6 +473,8 @@ class RayCaster(nn.Module):
             out.append(torch.from_numpy(to8b(col.cpu().numpy())).to(col.device))
         if return_density:
             out.append(dens)
+        if return_components:
+            out.append(components)
         return tuple(out)
 
 

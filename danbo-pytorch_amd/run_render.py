@@ -45,6 +45,9 @@ def config_parser():
     p.add_argument('--mesh_threshold', type=float, default=10.0, help='density of the extracted isosurface')
     p.add_argument('--mesh_normals', action='store_true', help='with --render_mesh: per-vertex normals in the .ply')
     p.add_argument('--mesh_colors', action='store_true', help='with --render_mesh: per-vertex colours (seen head-on) in the .ply')
+    p.add_argument('--mesh_keep_largest', action='store_true', help='with --render_mesh: drop the floaters -- keep only the largest '
+                   '6-connected component of the grid above the threshold (labelled and filtered on the device, before the extraction)')
+    p.add_argument('--mesh_min_points', type=int, default=0, help='with --render_mesh: drop every component of fewer grid points')
     p.add_argument('--mesh_render', nargs='?', const='normal', default=None, choices=['normal', 'color', 'flat'],
                    help='with --render_mesh: the turntable of every mesh (render_mesh.py) straight from the device tensors')
     p.add_argument('--mesh_render_res', nargs=2, type=int, default=[512, 512], help='(H, W) of the turntable frames')
@@ -268,7 +271,7 @@ def evaluate_metric(rgbs, accs, bboxes, gt_dict, basedir, on_device=False):
 
 @torch.no_grad()
 def render_mesh(basedir, render_kwargs, tensor_data, chunk=4096, radius=1.80, res=255, threshold=10., normals=False, colors=False,
-                turntable=None, turntable_res=(512, 512)):
+                turntable=None, turntable_res=(512, 512), keep_largest=False, min_points=0):
     """Density on a (res+1)^3 grid around every pose and its isosurface at `threshold` (reference :1266-1281: PyMCubes and trimesh
     there, the library's own extraction kernels and core/utils/mesh_io.py here): `meshes/NNN.ply`, vertices in [-0.5, 0.5]^3, and
     the clamped grid as `meshes/NNN_sigma.npy`.  normals / colors (--mesh_normals / --mesh_colors) add per-vertex unit normals --
@@ -276,21 +279,34 @@ def render_mesh(basedir, render_kwargs, tensor_data, chunk=4096, radius=1.80, re
     colours of the network seen along -normal (with the frame's frame code, where the network has them) to the vertex records.
     turntable ('normal' | 'color' | 'flat', --mesh_render): the 91 frames of the reference's render_mesh.py of every mesh, drawn
     from the device tensors (core/utils/mesh_render.py) into `mesh_render/NNN.npy`, uint8 [91,H,W,3]; it computes the normals or
-    colours it needs whether or not the .ply is asked to hold them."""
+    colours it needs whether or not the .ply is asked to hold them.
+    keep_largest / min_points (--mesh_keep_largest / --mesh_min_points): the grid's connected components above the threshold are
+    labelled on the device and the floaters set to 0 before the extraction (RayCaster.render_mesh_surface); the .ply, the
+    turntable and `NNN_sigma.npy` are the filtered grid's, and one line per mesh reports what was found and kept -- the one host
+    read of the filter, after the .ply is written."""
     caster = render_kwargs['ray_caster']
     os.makedirs(os.path.join(basedir, 'meshes'), exist_ok=True)
     want_n, want_c = normals or turntable == 'normal', colors or turntable == 'color'
     if turntable:
         os.makedirs(os.path.join(basedir, 'mesh_render'), exist_ok=True)
     kps, skts, bones, cams = tensor_data['kp'], tensor_data['skts'], tensor_data['bones'], tensor_data.get('cams')
+    filter_kw = dict(keep_largest=bool(keep_largest), min_component=int(min_points), return_components=True) \
+        if keep_largest or min_points else {}
     for i in range(len(kps)):
         cam = None if cams is None else cams[i % cams.shape[0]:i % cams.shape[0] + 1]
         verts, faces, *attrs, raw = caster(kps=kps[i:i + 1], skts=skts[i:i + 1], bones=bones[i:i + 1], radius=radius,
                                            render_kwargs=render_kwargs['preproc_kwargs'], res=res, netchunk=chunk, threshold=threshold,
-                                           return_density=True, normals=want_n, colors=want_c, cams=cam, fwd_type='mesh_surface')
+                                           return_density=True, normals=want_n, colors=want_c, cams=cam, fwd_type='mesh_surface',
+                                           **filter_kw)
+        if filter_kw:
+            components, raw = raw, attrs.pop()
         np.save(os.path.join(basedir, 'meshes', f'{i:03d}_sigma.npy'), np.maximum(raw.cpu().numpy(), 0))
         write_ply(os.path.join(basedir, 'meshes', f'{i:03d}.ply'), verts, faces, normals=attrs[0] if normals else None,
                   colors=attrs[-1] if colors else None)
+        if filter_kw:
+            (n_in, n_comp, biggest, label), (k_comp, k_pts) = (t.tolist() for t in components)
+            print(f'mesh {i:03d}: {n_in} grid points above the threshold in {n_comp} components (largest: {biggest} points, label '
+                  f'{label}); kept {k_comp} components, {k_pts} points')
         if turntable and len(verts) and len(faces):
             frames = render_turntable(verts, faces, normals=attrs[0] if want_n else None, colors=attrs[-1] if want_c else None,
                                       size=turntable_res, shade=turntable)
@@ -312,7 +328,7 @@ def run_render(argv=None):
     if args.render_mesh:
         render_mesh(basedir, render_kwargs, tensor_data, res=args.mesh_res, radius=args.mesh_radius, threshold=args.mesh_threshold,
                     normals=args.mesh_normals, colors=args.mesh_colors, turntable=args.mesh_render,
-                    turntable_res=tuple(args.mesh_render_res))
+                    turntable_res=tuple(args.mesh_render_res), keep_largest=args.mesh_keep_largest, min_points=args.mesh_min_points)
         return None
     render_kwargs = dict(render_kwargs, render_confd=args.render_confd, render_entropy=args.render_entropy,
                          part_valid_only=args.part_valid_only)

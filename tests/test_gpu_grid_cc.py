@@ -1,0 +1,294 @@
+"""Connected components of a density grid and the floater filter on the GPU (danbo_grid_cc_label / danbo_grid_cc_keep,
+core.grid_components, RayCaster.render_mesh_surface(keep_largest=...), run_render --mesh_keep_largest): the kernels against the serial
+restatement of csrc/grid_cc_math.hpp bit for bit -- labels, sizes, stats, the filtered grid by its bytes, kept -- through every
+layout, in place, on a second call and on another stream; guard words around every buffer; rejected arguments; the caster and
+the entry point.  Every comparison is exact."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import grid_cc_ref as ref
+import mesh_ref as m
+from helpers import DEV, EINVAL, ROOT, golden, T, same_bits
+
+pytestmark = pytest.mark.gpu
+F32 = np.float32
+INF = float("inf")
+GUARD32 = int(np.array(m.GUARD, np.uint32).view(np.int32))
+
+
+def entries():
+    from core import grid_components
+    return grid_components._entries()
+
+
+def stream_ptr():
+    from core import _hip
+    return _hip.stream()
+
+
+def guarded_t(n, dtype=torch.int32):
+    """-> (whole device buffer with N_GUARD guard words on either side, the view of the n payload words as `dtype`)"""
+    buf = torch.full((n + 2 * m.N_GUARD,), GUARD32, dtype=torch.int32, device=DEV)
+    return buf, buf[m.N_GUARD:m.N_GUARD + n].view(dtype)
+
+
+def intact(*bufs):
+    return all(bool((b[:m.N_GUARD] == GUARD32).all()) and bool((b[-m.N_GUARD:] == GUARD32).all()) for b in bufs)
+
+
+def device_grid(sigma, layout):
+    """the logical grid `sigma` on the device: 'contiguous', or 'transposed' = the x-y transposed view of a [ny,nx,nz] array (what
+    RayCaster.render_mesh_density returns)"""
+    if layout == "contiguous":
+        return T(sigma)
+    t = T(np.ascontiguousarray(sigma.transpose(1, 0, 2))).transpose(1, 0)
+    assert not t.is_contiguous() and t.stride(2) == 1
+    return t
+
+
+def grid_of(t, iso, floor):
+    return (t.data_ptr(), *t.shape, t.stride(0), t.stride(1), float(floor), float(iso))
+
+
+def gpu_label(t, iso, floor, want_sizes=True):
+    """the raw C call with guard words around labels, sizes, stats and a workspace of exactly danbo_grid_cc_workspace_bytes
+    -> labels, sizes (or None), stats as device tensors"""
+    n = t.numel()
+    n_bytes = entries()["danbo_grid_cc_workspace_bytes"](*t.shape)
+    assert n_bytes > 0 and n_bytes % 4 == 0
+    w_buf, ws = guarded_t(n_bytes // 4)
+    l_buf, labels = guarded_t(n)
+    s_buf, sizes = guarded_t(n)
+    t_buf, stats = guarded_t(4)
+    rc = entries()["danbo_grid_cc_label"](*grid_of(t, iso, floor), ws.data_ptr(), labels.data_ptr(), sizes.data_ptr() if want_sizes else None,
+                                          stats.data_ptr(), stream_ptr())
+    assert rc == 0, rc
+    torch.cuda.synchronize()
+    assert intact(w_buf, l_buf, s_buf, t_buf), "a guard word was overwritten"
+    if not want_sizes:
+        assert bool((sizes == GUARD32).all())
+    return labels.reshape(t.shape), sizes.reshape(t.shape) if want_sizes else None, stats
+
+
+def gpu_keep(t, iso, floor, labels, sizes, stats, keep_largest, min_points, fill, out="like"):
+    """the raw C call with guard words around out and kept; out: 'like' (sigma's strides), 'other' (the other of the two layouts:
+    strides that differ from sigma's), 'inplace' (a copy of sigma, filtered in place) -> out (numpy, logical order), kept (numpy)"""
+    nx, ny, nz = t.shape
+    o_buf, flat = guarded_t(t.numel(), torch.float32)
+    transposed = (not t.is_contiguous()) != (out == "other")
+    o = flat.reshape(ny, nx, nz).transpose(1, 0) if transposed else flat.reshape(nx, ny, nz)
+    src = t
+    if out == "inplace":
+        o.copy_(t)
+        src = o
+    assert (o.stride() == t.stride()) == (out != "other")
+    k_buf, kept = guarded_t(2)
+    rc = entries()["danbo_grid_cc_keep"](*grid_of(src, iso, floor), labels.data_ptr(), sizes.data_ptr(), stats.data_ptr(), int(keep_largest),
+                                         int(min_points), float(fill), o.data_ptr(), o.stride(0), o.stride(1), kept.data_ptr(), stream_ptr())
+    assert rc == 0, rc
+    torch.cuda.synchronize()
+    assert intact(o_buf, k_buf), "a guard word was overwritten"
+    return o.cpu().numpy().copy(), kept.cpu().numpy()
+
+
+KEEPS = ((True, 0), (False, 0), (False, 5))
+
+
+@pytest.mark.parametrize("name", sorted(ref.cases()))
+def test_kernels_equal_the_restatement_bitwise(name):
+    sigma, iso, floor = ref.cases()[name]
+    want_l, want_s, want_t = ref.reference(name)
+    fill = ref.default_fill(iso, floor)
+    want_keep = {k: ref.host_keep(sigma, iso, floor, want_l, want_s, want_t, *k, fill=fill) for k in KEEPS}
+    assert same_bits(want_keep[(False, 0)][0], np.ascontiguousarray(sigma))
+    for layout in ("contiguous", "transposed"):
+        t = device_grid(sigma, layout)
+        labels, sizes, stats = gpu_label(t, iso, floor)
+        got = [x.cpu().numpy() for x in (labels, sizes, stats)]
+        print(name, layout, "stats", got[2].tolist())
+        assert same_bits(got[0], want_l) and same_bits(got[1], want_s) and same_bits(got[2], want_t), (got[2], want_t)
+        for k in KEEPS:
+            for out in ("like", "other", "inplace"):
+                o, kept = gpu_keep(t, iso, floor, labels, sizes, stats, *k, fill, out=out)
+                assert same_bits(o, want_keep[k][0]) and same_bits(kept, want_keep[k][1]), (layout, k, out, kept, want_keep[k][1])
+    # without sizes: the same labels and stats, sizes untouched
+    labels, none, stats = gpu_label(t, iso, floor, want_sizes=False)
+    assert none is None and same_bits(labels.cpu().numpy(), want_l) and same_bits(stats.cpu().numpy(), want_t)
+
+
+def test_second_call_and_another_stream_give_the_same_bytes():
+    sigma, iso, floor = ref.cases()["bernoulli_0.5"]
+    t = device_grid(sigma, "contiguous")
+    first = gpu_label(t, iso, floor)
+    second = gpu_label(t, iso, floor)                     # one repeat, not a stress loop
+    assert all(torch.equal(a, b) for a, b in zip(first, second))
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        third = gpu_label(t, iso, floor)
+        o3, k3 = gpu_keep(t, iso, floor, *third, True, 0, -INF)
+    torch.cuda.current_stream().wait_stream(side)
+    assert all(torch.equal(a, b) for a, b in zip(first, third))
+    o1, k1 = gpu_keep(t, iso, floor, *first, True, 0, -INF)
+    assert same_bits(o1, o3) and same_bits(k1, k3)
+    assert all(same_bits(a.cpu().numpy(), b) for a, b in zip(first, ref.reference("bernoulli_0.5")))
+
+
+def test_rejected_arguments_leave_the_outputs_untouched():
+    sigma, iso, floor = ref.cases()["two_spheres"]
+    t = device_grid(sigma, "contiguous")
+    n = t.numel()
+    labels, sizes, stats = gpu_label(t, iso, floor)
+    bufs = {k: torch.full((n_words,), GUARD32, dtype=torch.int32, device=DEV)
+            for k, n_words in dict(ws=entries()["danbo_grid_cc_workspace_bytes"](*t.shape) // 4, labels=n, sizes=n, stats=4, out=n, kept=2).items()}
+    p = {k: b.data_ptr() for k, b in bufs.items()}
+    nx, ny, nz = t.shape
+    sx, sy = t.stride(0), t.stride(1)
+
+    def label(**kw):
+        a = dict(sigma=t.data_ptr(), nx=nx, ny=ny, nz=nz, sx=sx, sy=sy, floor=floor, iso=iso, ws=p["ws"], labels=p["labels"], sizes=p["sizes"],
+                 stats=p["stats"])
+        assert set(kw) <= set(a)
+        a.update(kw)
+        return entries()["danbo_grid_cc_label"](*a.values(), stream_ptr())
+
+    def keep(**kw):
+        a = dict(sigma=t.data_ptr(), nx=nx, ny=ny, nz=nz, sx=sx, sy=sy, floor=floor, iso=iso, labels=labels.data_ptr(), sizes=sizes.data_ptr(),
+                 stats=stats.data_ptr(), keep_largest=1, min_points=0, fill=-1., out=p["out"], osx=sx, osy=sy, kept=p["kept"])
+        assert set(kw) <= set(a)
+        a.update(kw)
+        return entries()["danbo_grid_cc_keep"](*a.values(), stream_ptr())
+
+    grid_cases = [dict(sigma=None), dict(sigma=t.data_ptr() + 2), dict(nx=1), dict(nz=1025), dict(ny=0), dict(sx=-sx), dict(sy=-1),
+                  dict(iso=INF), dict(iso=float("nan")), dict(floor=INF), dict(floor=float("nan"))]
+    for kw in grid_cases + [dict(ws=None), dict(ws=p["ws"] + 4), dict(labels=None), dict(labels=p["labels"] + 2), dict(sizes=p["sizes"] + 1),
+                            dict(stats=None), dict(stats=p["stats"] + 2)]:
+        assert label(**kw) == EINVAL, kw
+    for kw in grid_cases + [dict(labels=None), dict(sizes=None), dict(stats=None), dict(out=None), dict(out=p["out"] + 2), dict(kept=p["kept"] + 2),
+                            dict(min_points=-1), dict(fill=0.), dict(fill=3.), dict(fill=INF), dict(out=t.data_ptr() + 4),
+                            dict(out=t.data_ptr(), osx=nz, osy=nx * nz), dict(osy=nz - 1), dict(osx=0)]:
+        assert keep(**kw) == EINVAL, kw
+    torch.cuda.synchronize()
+    assert all(bool((b == GUARD32).all()) for b in bufs.values())
+    # and the calls they were variations of are accepted
+    assert label() == 0 and keep() == 0 and keep(kept=None) == 0 and keep(fill=float("nan")) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(bufs["labels"].reshape(t.shape), labels) and torch.equal(bufs["stats"], stats)
+
+
+def test_python_wrappers():
+    from core.grid_components import grid_components, keep_components
+    sigma, iso, floor = ref.cases()["noise0"]
+    want = ref.reference("noise0")
+    for layout in ("contiguous", "transposed"):
+        t = device_grid(sigma, layout)
+        labels, sizes, stats = grid_components(t, iso)
+        assert labels.is_contiguous() and sizes.is_contiguous() and labels.dtype == sizes.dtype == stats.dtype == torch.int32
+        assert all(same_bits(a.cpu().numpy(), b) for a, b in zip((labels, sizes, stats), want))
+        out, kept = keep_components(t, iso, -INF, labels, sizes, stats, keep_largest=True)
+        assert out.stride() == t.stride() and out.data_ptr() != t.data_ptr()
+        want_out, want_kept = ref.host_keep(sigma, iso, floor, *want, keep_largest=True, fill=-INF)
+        assert same_bits(out.cpu().numpy(), want_out) and same_bits(kept.cpu().numpy(), want_kept)
+        same, _ = keep_components(t, iso, -INF, labels, sizes, stats)
+        assert same_bits(same.cpu().numpy(), np.ascontiguousarray(sigma))
+        work = t.clone(memory_format=torch.preserve_format)
+        got, kept2 = keep_components(work, iso, -INF, labels, sizes, stats, min_points=5, fill=-2., out=work)
+        assert got is work and same_bits(work.cpu().numpy(), ref.host_keep(sigma, iso, floor, *want, min_points=5, fill=-2.)[0])
+    # floor = 0, iso = 10: the default fill is the floor
+    s2, iso2, floor2 = ref.cases()["floor0_iso10_3x5x65"]
+    t2 = T(s2)
+    l2 = grid_components(t2, iso2, floor=floor2)
+    out2, kept2 = keep_components(t2, iso2, floor2, *l2, keep_largest=True)
+    want2 = ref.host_keep(s2, iso2, floor2, *ref.reference("floor0_iso10_3x5x65"), keep_largest=True, fill=0.)
+    assert same_bits(out2.cpu().numpy(), want2[0]) and same_bits(kept2.cpu().numpy(), want2[1])
+    with pytest.raises(ValueError, match="not outside"):
+        keep_components(t2, iso2, floor2, *l2, fill=10.)
+    with pytest.raises(ValueError, match="min_points"):
+        keep_components(t2, iso2, floor2, *l2, min_points=-1)
+    with pytest.raises(ValueError, match="float32"):
+        grid_components(t2.double(), iso2)
+    with pytest.raises(ValueError, match="innermost stride"):
+        grid_components(t2.transpose(1, 2), iso2)
+    with pytest.raises(ValueError, match="labels"):
+        keep_components(t2, iso2, floor2, l2[0].reshape(-1), l2[1], l2[2])
+    from core import _hip
+    with pytest.raises(_hip.HipError, match="unsupported grid"):
+        grid_components(torch.zeros(1, 4, 4, device=DEV), 0.)
+
+
+# ----------------------------------------------------------------------------- the caster
+def test_caster_filters_before_the_extraction():
+    from core import hip_ops
+    from test_gpu_modules import build
+    g = golden("danbo_mesh")
+    caster, _ = build("h36m_zju/danbo_base.txt", g)
+    res = 64
+    args = (T(g["kps"][:1]), T(g["skts"][:1]), T(g["bones"][:1]))
+    kw = dict(fwd_type="mesh_surface", radius=float(g["radius"]), res=res)
+    dens = caster(*args, fwd_type="mesh", radius=float(g["radius"]), res=res)
+    grid = dens.cpu().numpy()
+    thr = float(F32(np.median(grid[grid > 0])))
+    # the defaults change nothing
+    plain = caster(*args, threshold=thr, normals=True, return_density=True, **kw)
+    explicit = caster(*args, threshold=thr, normals=True, return_density=True, keep_largest=False, min_component=0, **kw)
+    assert len(plain) == len(explicit) == 4 and all(torch.equal(a, b) for a, b in zip(plain, explicit))
+    assert torch.equal(plain[3], dens) and plain[3].stride() == dens.stride()
+    # keep_largest: the returned grid is the restatement's filtered grid, and the mesh is that grid's
+    verts, faces, normals, filtered, (stats, kept) = caster(*args, threshold=thr, normals=True, return_density=True, keep_largest=True,
+                                                           return_components=True, **kw)
+    assert filtered.stride() == dens.stride() and filtered.data_ptr() != dens.data_ptr()
+    sigma = np.ascontiguousarray(grid)
+    labels, sizes, want_stats = ref.host_label(sigma, thr, 0.)
+    want_grid, want_kept = ref.host_keep(sigma, thr, 0., labels, sizes, want_stats, keep_largest=True, fill=0.)
+    print("golden pose: threshold", thr, "stats", stats.tolist(), "kept", kept.tolist(), "V", len(verts), "of", len(plain[0]))
+    assert same_bits(filtered.cpu().numpy(), want_grid) and same_bits(stats.cpu().numpy(), want_stats) and same_bits(kept.cpu().numpy(), want_kept)
+    assert kept.tolist()[0] == 1 and ref.host_label(want_grid, thr, 0.)[2][1] == 1
+    again = hip_ops.marching_cubes(device_grid(want_grid, "transposed"), thr, floor=0., scale=1. / res, offset=(-.5, -.5, -.5), normals=True)
+    assert all(torch.equal(a, b) for a, b in zip((verts, faces, normals), again))
+    # every vertex of the filtered mesh is a vertex of the unfiltered one
+    rows = {r.tobytes() for r in plain[0].cpu().numpy()}
+    assert all(r.tobytes() in rows for r in verts.cpu().numpy())
+    # min_component alone
+    v2, f2, d2 = caster(*args, threshold=thr, return_density=True, min_component=int(want_stats[2]), **kw)
+    assert torch.equal(d2, filtered) and torch.equal(v2, verts) and torch.equal(f2, faces)
+
+
+# ----------------------------------------------------------------------------- the entry point
+def test_run_render_keeps_the_largest_component(tmp_path, capsys):
+    import run_nerf
+    import run_render
+    from core.utils.mesh_io import read_ply
+    cfg = os.path.join(ROOT, "danbo-pytorch_amd", "configs", "surreal", "danbo_fast.txt")
+    run_nerf.train(["--config", cfg, "--basedir", str(tmp_path), "--expname", "demo", "--syn_poses", "2", "--syn_cams", "2",
+                    "--syn_res", "32", "--syn_rest_scale", "0.714", "--N_rand", "512", "--N_sample_images", "4", "--i_print", "10",
+                    "--i_weights", "20", "--i_testset", "20", "--render_factor", "0", "--n_iters", "20"])
+    log = tmp_path / "demo"
+    base = ["--nerf_args", str(log / "args.txt"), "--ckptpath", str(log / "000020.tar"), "--dataset", "synthetic", "--entry", "val",
+            "--outputdir", str(tmp_path / "out"), "--render_type", "selected", "--selected_idxs", "1", "--render_mesh", "--mesh_res", "31",
+            "--mesh_radius", "1.2"]
+    run_render.run_render(base + ["--runname", "plain"])
+    sig = np.load(tmp_path / "out" / "plain" / "meshes" / "000_sigma.npy")
+    assert sig.shape == (32, 32, 32) and sig.max() > 0
+    thr = float(F32(np.median(sig[sig > 0])))          # (an untrained synthetic network need not reach the reference's 10)
+    capsys.readouterr()
+    run_render.run_render(base + ["--runname", "kept", "--mesh_threshold", repr(thr), "--mesh_keep_largest", "--mesh_render",
+                                  "--mesh_render_res", "48", "64"])
+    line = [x for x in capsys.readouterr().out.splitlines() if x.startswith("mesh 000:")]
+    d = tmp_path / "out" / "kept" / "meshes"
+    sig2 = np.load(d / "000_sigma.npy")
+    labels, sizes, stats = ref.predict(sig, thr)
+    lab2, n2 = ref.ndimage.label(sig2 >= F32(thr))
+    print("run_render --mesh_keep_largest: threshold", thr, "stats", stats.tolist(), "|", line)
+    assert n2 == 1 and stats[1] >= 1
+    assert np.array_equal(sig2 >= F32(thr), labels == stats[3]) and np.array_equal(sig2[sig2 >= F32(thr)], sig[labels == stats[3]])
+    assert np.all(sig2[(labels >= 0) & (labels != stats[3])] == 0) and np.array_equal(sig2[labels < 0], sig[labels < 0])
+    assert len(line) == 1 and f"{stats[0]} grid points" in line[0] and f"in {stats[1]} components" in line[0] and f"kept 1 components, {stats[2]} points" in line[0]
+    v, f = read_ply(str(d / "000.ply"))
+    hv, hf = m.host_extract(sig2, thr, scale=1. / 31, offset=(-.5, -.5, -.5))
+    assert len(v) > 0 and same_bits(v, hv) and same_bits(f, hf)
+    # --mesh_render needs no change: the turntable is drawn from the filtered mesh (a 31-point blob: it may cover no pixel centre)
+    frames = np.load(tmp_path / "out" / "kept" / "mesh_render" / "000.npy")
+    assert frames.shape == (91, 48, 64, 3) and frames.dtype == np.uint8
