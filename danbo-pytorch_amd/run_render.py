@@ -9,8 +9,9 @@ sequence -- `bullet` (camera ring around selected poses), `interpolate` (axis-an
 (camera wobbling around its position), `val` /
 `selected` (the data's own cameras) -- or sampled on a density grid (`--render_mesh`).  The sequence generators take arrays
 instead of the reference's HDF5 paths (no h5py / deepdish here); `--dataset synthetic` builds them from seeded poses, `--dataset
-npz --entry file.npz` reads them.  Outputs: `image/`, `acc/` as .npy stacks (no imageio here), `bboxes.npy`, and with
-`--eval` `scores.npy` + `score_final.txt` like the reference.
+npz --entry file.npz` reads them.  Outputs: `image/`, `acc/` as .npy stacks (no imageio here), `bboxes.npy`, with
+`--eval` `scores.npy` + `score_final.txt` like the reference, and with `--render_skel` the reference's `skel/` as `skel.npy`:
+every frame with its posed skeleton drawn over it on the device (core/utils/skeleton_draw.py).
 """
 import argparse
 import os
@@ -26,6 +27,7 @@ from core.raycasters import create_raycaster  # noqa: E402
 from core.utils.evaluation_helpers import evaluate_in_boxes, evaluate_in_boxes_device  # noqa: E402
 from core.utils.mesh_io import write_ply  # noqa: E402
 from core.utils.mesh_render import render_turntable  # noqa: E402
+from core.utils.skeleton_draw import draw_skeletons_3d  # noqa: E402
 from core.utils.skeleton_utils import get_smpl_l2ws  # noqa: E402
 from run_nerf import render_path  # noqa: E402
 
@@ -57,6 +59,10 @@ def config_parser():
                    'bone) to red (uniform); --render_confd wins when both are given')
     p.add_argument('--part_valid_only', action='store_true', help='with --render_confd / --render_entropy: only the bones whose '
                    'volume holds the sample take part')
+    p.add_argument('--render_skel', action='store_true', help='also save skel.npy: every frame with its posed skeleton drawn over it '
+                   '(the reference\'s skel/ output), made on the device')
+    p.add_argument('--skel_width', type=int, default=3, help='with --render_skel: width of the bones in pixels (1 .. 64)')
+    p.add_argument('--skel_flip', action='store_true', help='with --render_skel: the reference\'s second set of colours')
     p.add_argument('--selected_idxs', nargs='+', type=int, default=None)
     p.add_argument('--selected_framecode', type=int, default=None)
     p.add_argument('--n_bullet', type=int, default=10)
@@ -337,6 +343,13 @@ def run_render(argv=None):
     scores = None
     if gt_dict['gt_paths'] is not None and args.eval:
         scores = evaluate_metric(rgbs, accs, bboxes, gt_dict, basedir, on_device=args.eval_device)
+    if args.render_skel and not args.no_save:
+        # the overlay from the frames where they are: device frames as they are (quantised in the draw), host frames as the uint8
+        # image.npy holds; only the finished uint8 overlay crosses to the host
+        frames = rgbs if args.eval_device else (rgbs * 255).astype(np.uint8)
+        skel = draw_skeletons_3d(frames, render_data['kp'], render_data['render_poses'], *render_data['hwf'],
+                                 centers=render_data['centers'], width=args.skel_width, flip=args.skel_flip)
+        np.save(os.path.join(basedir, 'skel.npy'), skel.cpu().numpy())
     if args.eval_device and not args.no_save:          # the frames leave the device only to be saved
         rgbs, accs = rgbs.cpu().numpy(), accs.cpu().numpy()
     if not args.no_save:
