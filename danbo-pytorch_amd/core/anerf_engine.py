@@ -9,6 +9,7 @@ every sample is evaluated, exactly as in the reference (core/networks/nerf.py:10
 import torch
 
 from . import hip_ops as ops
+from .depth_maps import composite_depth
 from .render_engine import RenderEngine
 
 
@@ -179,7 +180,8 @@ class AnerfEngine(RenderEngine):
         return ops.near_far_cylinder(rays_o, rays_d, cyls, near0, far0, chunk)
 
     def render(self, rays_o, rays_d, skts, bones, cyls, cam_idx=None, N_samples=None, N_importance=None, chunk=4096,
-               near_far=None, keep=False, **_):
+               near_far=None, keep=False, depth=False, depth_level=0.5, **_):
+        """depth / depth_level: as DanboEngine.render -- depth_map and depth_med from the final composite's weights"""
         S, Sf, B, act = self._sampling(N_samples, N_importance)
         self.refresh()
         near, far = self.near_far(rays_o, rays_d, cyls, skts, 0.0, 1.0, chunk) if near_far is None else near_far
@@ -192,6 +194,8 @@ class AnerfEngine(RenderEngine):
         raw_all = ops.merge_samples(raw, raw_f, order)
         out = ops.composite(raw_all, z_all, rays_d, B, act=act)
         ret = self.frame_result(out, out0)
+        if depth:
+            ret["depth_map"], ret["depth_med"] = composite_depth(out["weights"], z_all, depth_level)
         if keep:
             ret.update(near=near, far=far, z_coarse=z, raw_coarse=raw, weights_coarse=out0["weights"], z_fine=z_fine,
                        z_sorted=z_all, sorted_idxs=order, raw_fine=raw_f, raw_sorted=raw_all)

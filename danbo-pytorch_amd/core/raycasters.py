@@ -268,13 +268,18 @@ class RayCaster(nn.Module):
             return {}
         return dict(part_map='confd' if render_confd else 'entropy', part_valid_only=bool(part_valid_only))
 
+    @staticmethod
+    def _depth_kwargs(render_depth, depth_level):
+        """render_depth / depth_level as the engines' depth arguments (every engine takes them); both join the HIP-graph key"""
+        return dict(depth=True, depth_level=float(depth_level)) if render_depth else {}
+
     _per_pose = staticmethod(ops.per_pose)
 
     def render_rays(self, ray_batch, N_samples, kp_batch, skts=None, cyls=None, bones=None, cams=None,
                     subject_idxs=None, retraw=False, lindisp=False, perturb=0., N_importance=0, network_fine=None,
                     raw_noise_std=0., ray_noise_std=0., verbose=False, ext_scale=0.001, pytest=False, N_uniques=1,
                     render_confd=False, render_entropy=False, part_valid_only=False, preproc_kwargs={}, netchunk=1024 * 64,
-                    nerf_type="nerf", **kwargs):
+                    nerf_type="nerf", render_depth=False, depth_level=0.5, **kwargs):
         if N_importance <= 0:
             raise NotImplementedError("N_importance=0 raises in the reference too (raycasters.py:377)")
         if perturb or raw_noise_std or ray_noise_std or lindisp:
@@ -284,6 +289,9 @@ class RayCaster(nn.Module):
         # would have made of them: rgb_map / rgb0 become the bone-assignment map (DanboEngine.render(part_map=...)).
         eng, fine = self._engines(preproc_kwargs)
         part = self._part_kwargs(eng, render_confd, render_entropy, part_valid_only)
+        # render_depth: the result gains depth_map / depth_med (engine render(depth=True)), the route render_confd takes; depth may
+        # be combined with a part map
+        part.update(self._depth_kwargs(render_depth, depth_level))
         G = int(N_uniques)
         skts_g, bones_g, cyls_g = self._per_pose(skts, G), self._per_pose(bones, G), self._per_pose(cyls, G)
         R = ray_batch.shape[0]
@@ -313,7 +321,7 @@ class RayCaster(nn.Module):
     def render_rays_whole(self, ray_batch, chunk, N_samples=None, kp_batch=None, skts=None, cyls=None, bones=None, cams=None,
                           lindisp=False, perturb=0., N_importance=0, raw_noise_std=0., ray_noise_std=0., N_uniques=1,
                           preproc_kwargs={}, fwd_type='', rays=None, near_far0=None, render_confd=False, render_entropy=False,
-                          part_valid_only=False, **kwargs):
+                          part_valid_only=False, render_depth=False, depth_level=0.5, **kwargs):
         """`trainer.batchify_rays`' loop over `chunk`-ray casts as ONE cast of all rays, when that is the same computation, else
         None (the caller loops).  It is the same when every ray belongs to one pose (so a chunk's N_uniques = 1 whatever the
         chunking) and the engine is the DANBO engine: every stage is per ray or per sample except the cylinder bounds' nan-mean
@@ -325,6 +333,7 @@ class RayCaster(nn.Module):
         if not isinstance(eng, DanboEngine) or N_samples > 256 or N_importance > 64:
             return None
         part = self._part_kwargs(eng, render_confd, render_entropy, part_valid_only)
+        part.update(self._depth_kwargs(render_depth, depth_level))
         skts_g, bones_g, cyls_g = skts[:1].contiguous(), bones[:1].contiguous(), cyls[:1].contiguous()
         chunk = int(chunk)
         R = rays[0].shape[0] if rays is not None else ray_batch.shape[0]

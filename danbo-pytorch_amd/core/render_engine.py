@@ -15,6 +15,7 @@ import torch
 
 from . import _hip
 from . import hip_ops as ops
+from .depth_maps import composite_depth
 
 
 class RenderEngine:
@@ -67,7 +68,8 @@ class RenderEngine:
         return rgb, (None if dense else ex["valid_bits"])
 
     def render_two_net(self, fine, rays_o, rays_d, skts, bones, cyls, cam_idx=None, N_samples=None, N_importance=None,
-                       chunk=4096, near_far=None, dense=False, keep=False, part_map=None, part_valid_only=False):
+                       chunk=4096, near_far=None, dense=False, keep=False, part_map=None, part_valid_only=False, depth=False,
+                       depth_level=0.5):
         """The hierarchical render of a caster with a separate fine network (single_net = False, reference raycasters.py:330-377):
         this engine's network on the S coarse samples and their composite (rgb0 ...); the two-network pdf (is_only=False) for the
         Sf importance depths; `fine` -- the fine network's engine -- on ALL S + Sf samples in sorted order, composited as they
@@ -75,7 +77,7 @@ class RenderEngine:
         use_volume_near_far.  No rays of constants here: the fine pass reads z_sorted of every ray, so every ray is resampled.
         part_map / part_valid_only: as DanboEngine.render -- rgb0 is the part map of the coarse network's logits under the coarse
         weights, rgb_map that of the FINE network's logits on the S + Sf sorted samples under the final weights (no merge); dense
-        unless both networks allow the culled path."""
+        unless both networks allow the culled path.  depth / depth_level: as DanboEngine.render, from the fine network's weights."""
         S, Sf, B, act = self._sampling(N_samples, N_importance)
         self.refresh()
         fine.refresh()
@@ -103,6 +105,8 @@ class RenderEngine:
             col_f, cb_f = self._part_colors(pex_f, S + Sf, part, part_valid_only, dense)
             ops.composite_colors(col_f, out["weights"], bits_a=cb_f, out=out["rgb_map"])
         ret = self.frame_result(out, out0)
+        if depth:
+            ret["depth_map"], ret["depth_med"] = composite_depth(out["weights"], z_all, depth_level)
         if keep and part:
             ret.update(confd_coarse=pex["confd_rows"], confd_fine=pex_f["confd_rows"], list_coarse=pex["list"],
                        list_fine=pex_f["list"])
@@ -430,7 +434,8 @@ class DanboEngine(RenderEngine):
         return near, far
 
     def render(self, rays_o, rays_d, skts, bones, cyls, cam_idx=None, N_samples=None, N_importance=None,
-               chunk=4096, near_far=None, dense=False, keep=False, part_map=None, part_valid_only=False):
+               chunk=4096, near_far=None, dense=False, keep=False, part_map=None, part_valid_only=False, depth=False,
+               depth_level=0.5):
         """The two-pass render of one network (reference raycasters.py:245-396, eval) -> frame_result's dict.
 
         part_map: None | 'confd' | 'entropy' -- rgb_map and rgb0 become the bone-assignment map instead of the colour image
@@ -444,7 +449,13 @@ class DanboEngine(RenderEngine):
         exactly +0, which holds for relu density with an empty-space density <= 0 (`empty_density_le0`).  Otherwise -- softplus,
         or a positive empty-space density -- a part-map render runs dense=True, so that every sample has logits.
         keep=True additionally returns what the colouring read: confd_coarse / confd_fine (K2's rows) and list_coarse /
-        list_fine (row -> sample; None when dense), beside count_*, valid_bits and valid_bits_fine."""
+        list_fine (row -> sample; None when dense), beside count_*, valid_bits and valid_bits_fine.
+
+        depth: the result gains depth_map [R] = sum_k w_k z_k (the reference's depth_map, nerf.py:337) and depth_med [R], the depth
+        of the first sorted position whose prefix of the weights reaches depth_level (0.5: the median; +0 where acc stays below
+        it) -- one more launch over the FINAL composite's weights and sorted depths (core/depth_maps.py), which walks the list of
+        the rays of constants where there is one: their depths are the +0 the outputs start from.  Nothing else changes: neither
+        lazy nor the rays of constants are switched off, and every other output is bit for bit the plain render's."""
         S, Sf, B, act = self._sampling(N_samples, N_importance)
         self.refresh()
         part = self._part_mode(part_map)
@@ -507,6 +518,8 @@ class DanboEngine(RenderEngine):
             ops.composite_colors(col, out0["weights"], bits_a=cb, flat=flat, out=out0["rgb_map"])
             ops.composite_colors(col, out["weights"], col_f, order, cb, cb_f, flat=flat, out=out["rgb_map"])
         ret = self.frame_result(out, out0)
+        if depth:
+            ret["depth_map"], ret["depth_med"] = composite_depth(out["weights"], z_all, depth_level, flat=flat)
         if keep:
             ret.update(near=near, far=far, z_coarse=z, raw_coarse=raw, weights_coarse=out0["weights"], z_fine=z_fine,
                        z_sorted=z_all, sorted_idxs=order, raw_fine=raw_f, raw_sorted=out.get("raw_sorted"),

@@ -31,11 +31,14 @@ from core.utils.ray_utils import kp_to_valid_rays  # noqa: E402
 
 def render_path(render_poses, hwf, chunk, render_kwargs, centers=None, kp=None, skts=None, cyls=None, bones=None, gt_imgs=None,
                 bg_imgs=None, bg_indices=None, cams=None, subject_idxs=None, render_factor=0, white_bkgd=False, ret_acc=False,
-                ext_scale=0.00035, base_bg=1.0, device_out=False):
+                ext_scale=0.00035, base_bg=1.0, device_out=False, ret_depth=False):
     """One image per camera in `render_poses`: only the pixels inside the 2-D box of the pose's bounding cylinder are cast,
     the rest of the image is the background (`bg_imgs[bg_indices[i]]` resized, white, or black).  Pose tensors with fewer
     entries than cameras are cycled (`i % n`).  -> rgbs [N,H,W,3], disps [N,H,W,1], accs, valid_idxs, bboxes: numpy arrays, one
-    device-to-host copy per frame; with device_out the stacked DEVICE tensors (nan_to_num applied there), nothing copied."""
+    device-to-host copy per frame; with device_out the stacked DEVICE tensors (nan_to_num applied there), nothing copied.
+    ret_depth: the rays are cast with render_depth=True (depth_level from render_kwargs, default 0.5) and a sixth element follows:
+    dict(depth=[N,H,W] the expected depth sum w z, depth_med=[N,H,W] the level depth, cast=[N,H,W] bool: the pixel was cast),
+    assembled like the acc frames -- 0 outside the cast box -- and on the device or the host as the other frames are."""
     H, W, focal = hwf
     if render_factor != 0:
         H, W = H // render_factor, W // render_factor
@@ -53,6 +56,9 @@ def render_path(render_poses, hwf, chunk, render_kwargs, centers=None, kp=None, 
 
     out = (lambda x: x) if device_out else (lambda x: x.cpu().numpy())      # a frame stays where it is, or crosses to the host
     rgbs, disps, accs = [], [], []
+    depths = dict(depth=[], depth_med=[], cast=[])
+    if ret_depth:
+        render_kwargs = dict(render_kwargs, render_depth=True)
     for i, c2w in enumerate(render_poses):
         h = H if isinstance(H, int) else int(H[i])
         w = W if isinstance(W, int) else int(W[i])
@@ -65,19 +71,28 @@ def render_path(render_poses, hwf, chunk, render_kwargs, centers=None, kp=None, 
         else:
             rgb_img = torch.full((h * w, 3), 1. if white_bkgd else 0., device=dev)
         disp_img, acc_img = torch.zeros(h * w, device=dev), torch.zeros(h * w, device=dev)
+        if ret_depth:
+            depth_img, med_img = torch.zeros(h * w, device=dev), torch.zeros(h * w, device=dev)
+            cast_img = torch.zeros(h * w, device=dev, dtype=torch.bool)
         if n > 0:
             ret = render(h, w, focal, rays=(rays_o, rays_d), chunk=chunk, c2w=c2w[:3, :4], kp_batch=per_image(kp, i, n),
                          skts=per_image(skts, i, n), cyls=per_image(cyls, i, n), cams=per_image(cams, i, n),
                          subject_idxs=per_image(subject_idxs, i, n), bones=per_image(bones, i, n), **render_kwargs)
             rgb_img[idx] = ret['rgb_map'] + (1. - ret['acc_map'][..., None]) * rgb_img[idx]
             disp_img[idx], acc_img[idx] = ret['disp_map'], ret['acc_map']
+            if ret_depth:
+                depth_img[idx], med_img[idx], cast_img[idx] = ret['depth_map'], ret['depth_med'], True
         rgbs.append(out(rgb_img.view(h, w, 3)))
         disps.append(out(disp_img.view(h, w, 1)))
         if ret_acc:
             accs.append(out(acc_img.view(h, w, 1)))
+        if ret_depth:
+            for k, img in (('depth', depth_img), ('depth_med', med_img), ('cast', cast_img)):
+                depths[k].append(out(img.view(h, w)))
     stack, nan_to_num = (torch.stack, torch.nan_to_num) if device_out else (np.stack, np.nan_to_num)
     rgbs, disps = stack(rgbs, 0), nan_to_num(stack(disps, 0), nan=0.)
-    return rgbs, disps, (stack(accs, 0) if ret_acc else accs), valid_idxs, bboxes
+    frames = (rgbs, disps, (stack(accs, 0) if ret_acc else accs), valid_idxs, bboxes)
+    return frames + ({k: stack(v, 0) for k, v in depths.items()},) if ret_depth else frames
 
 
 def render_testset(poses, hwf, args, render_kwargs, kps=None, skts=None, cyls=None, cams=None, bones=None, subject_idxs=None,

@@ -11,7 +11,10 @@ sequence -- `bullet` (camera ring around selected poses), `interpolate` (axis-an
 instead of the reference's HDF5 paths (no h5py / deepdish here); `--dataset synthetic` builds them from seeded poses, `--dataset
 npz --entry file.npz` reads them.  Outputs: `image/`, `acc/` as .npy stacks (no imageio here), `bboxes.npy`, with
 `--eval` `scores.npy` + `score_final.txt` like the reference, and with `--render_skel` the reference's `skel/` as `skel.npy`:
-every frame with its posed skeleton drawn over it on the device (core/utils/skeleton_draw.py).
+every frame with its posed skeleton drawn over it on the device (core/utils/skeleton_draw.py).  `--render_depth` adds `depth.npy`
+(the expected depth sum w z of every pixel of the rendered camera, float32 [N,H,W], 0 outside the cast box) and `depth_med.npy`
+(the depth at which the accumulated weight reaches `--depth_level`), `--render_normal` adds `normal.npy` (uint8 [N,H,W,3]): the
+normal map of the depth frames, made on the device (core/depth_maps.py).
 """
 import argparse
 import os
@@ -22,6 +25,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from core.config import config_parser as nerf_config_parser, txt_to_argstring  # noqa: E402
+from core.depth_maps import normal_maps  # noqa: E402
 from core.load_data import PoseImageDataset, generate_bullet_time, get_dataset  # noqa: E402
 from core.raycasters import create_raycaster  # noqa: E402
 from core.utils.evaluation_helpers import evaluate_in_boxes, evaluate_in_boxes_device  # noqa: E402
@@ -63,6 +67,17 @@ def config_parser():
                    '(the reference\'s skel/ output), made on the device')
     p.add_argument('--skel_width', type=int, default=3, help='with --render_skel: width of the bones in pixels (1 .. 64)')
     p.add_argument('--skel_flip', action='store_true', help='with --render_skel: the reference\'s second set of colours')
+    p.add_argument('--render_depth', action='store_true', help='also save depth.npy (float32 [N,H,W]: the expected depth sum w z of '
+                   'every pixel, 0 outside the cast box) and depth_med.npy (the depth where the accumulated weight reaches --depth_level)')
+    p.add_argument('--depth_level', type=float, default=0.5, help='with --render_depth: the level of depth_med.npy in (0, 1]; 0.5 is '
+                   'the median depth')
+    p.add_argument('--render_normal', action='store_true', help='also save normal.npy (uint8 [N,H,W,3]): the normal map of the '
+                   'rendered depth, 0.5 n + 0.5, white where a pixel has no normal; made on the device')
+    p.add_argument('--normal_space', type=str, default='camera', choices=['camera', 'world'], help='with --render_normal: camera '
+                   'space (x right, y up, z towards the camera) or world space (comparable with the mesh turntable)')
+    p.add_argument('--normal_acc_min', type=float, default=0.5, help='with --render_normal: a pixel below this opacity has no normal')
+    p.add_argument('--normal_jump', type=float, default=0., help='with --render_normal: > 0 leaves out neighbours whose depth differs '
+                   'by more (no normals across depth edges)')
     p.add_argument('--selected_idxs', nargs='+', type=int, default=None)
     p.add_argument('--selected_framecode', type=int, default=None)
     p.add_argument('--n_bullet', type=int, default=10)
@@ -319,6 +334,23 @@ def render_mesh(basedir, render_kwargs, tensor_data, chunk=4096, radius=1.80, re
             np.save(os.path.join(basedir, 'mesh_render', f'{i:03d}.npy'), frames.cpu().numpy())
 
 
+def save_depth_maps(args, basedir, geo, accs, render_data, device):
+    """depth.npy / depth_med.npy (--render_depth) and normal.npy (--render_normal) from render_path's depth frames `geo` and acc
+    frames `accs` [N,H,W,1], wherever those lie: the normals are made on the device (host frames are uploaded) with every frame's
+    c2w, focal and centre, and only the finished uint8 map crosses back."""
+    host = lambda x: x.cpu().numpy() if isinstance(x, torch.Tensor) else x      # noqa: E731
+    if args.render_depth:
+        np.save(os.path.join(basedir, 'depth.npy'), host(geo['depth']).astype(np.float32))
+        np.save(os.path.join(basedir, 'depth_med.npy'), host(geo['depth_med']).astype(np.float32))
+    if args.render_normal:
+        dev = lambda x: torch.as_tensor(x).to(device)      # noqa: E731
+        H, W, focals = render_data['hwf']
+        rgb = normal_maps(dev(geo['depth']).float(), dev(accs).float()[..., 0], render_data['render_poses'], focals,
+                          centers=render_data['centers'], cast_mask=dev(geo['cast']), acc_min=args.normal_acc_min,
+                          jump=args.normal_jump, space=args.normal_space)
+        np.save(os.path.join(basedir, 'normal.npy'), (rgb * 255).to(torch.uint8).cpu().numpy())
+
+
 def run_render(argv=None):
     args = config_parser().parse_args(argv)
     if not torch.cuda.is_available():
@@ -338,8 +370,14 @@ def run_render(argv=None):
         return None
     render_kwargs = dict(render_kwargs, render_confd=args.render_confd, render_entropy=args.render_entropy,
                          part_valid_only=args.part_valid_only)
-    rgbs, _, accs, _, bboxes = render_path(render_kwargs=render_kwargs, chunk=nerf_args.chunk, ext_scale=nerf_args.ext_scale,
-                                           ret_acc=True, white_bkgd=args.white_bkgd, device_out=args.eval_device, **tensor_data)
+    want_depth = args.render_depth or args.render_normal
+    if want_depth:
+        render_kwargs['depth_level'] = args.depth_level
+    rgbs, _, accs, _, bboxes, *geo = render_path(render_kwargs=render_kwargs, chunk=nerf_args.chunk, ext_scale=nerf_args.ext_scale,
+                                                 ret_acc=True, white_bkgd=args.white_bkgd, device_out=args.eval_device,
+                                                 ret_depth=want_depth, **tensor_data)
+    if want_depth and not args.no_save:
+        save_depth_maps(args, basedir, geo[0], accs, render_data, device)
     scores = None
     if gt_dict['gt_paths'] is not None and args.eval:
         scores = evaluate_metric(rgbs, accs, bboxes, gt_dict, basedir, on_device=args.eval_device)
