@@ -14,9 +14,8 @@ The header is $DANBO_HIP_HEADER, else danbo_hip.h beside the library, else inclu
 RESTYPES, STRUCTS and C are the statement of danbo_hip.h alone.  The entry points of a later feature stand in a header of their own
 beside it (a satellite), bound the same way and reached as `header("danbo_x.h").signatures / .restypes / .C / .path`: a satellite
 declares no struct, and no function or constant that an earlier header declares.  A new header is named in HEADERS, nowhere else.
-A header outside that pinned set (danbo_batch.h, danbo_grid_cc.h) is bound by the module that uses it: `bind_headers([HEADER_PATH, <path beside
-it>])[1]` gives the same parser and the same satellite rule, and the user sets argtypes / restype on `lib()`'s handle at first use.
-`lib()` refuses a library whose danbo_abi_version() is not the header's DANBO_ABI_VERSION (a stale build).
+`lib()` sets the types of every entry of every header of HEADERS and refuses a stale build: a library whose danbo_abi_version() is
+not the header's DANBO_ABI_VERSION, or one that lacks an entry a header declares.
 
 The library is the only compute backend of this package: there is NO PyTorch/CPU fallback.  `lib()` raises if the shared object is
 missing, and every wrapper in hip_ops raises if a tensor is not a CUDA(HIP) tensor.
@@ -202,7 +201,8 @@ def _header_path():
                        + "; set DANBO_HIP_HEADER or put the header beside the library")
 
 
-HEADERS = ("danbo_hip.h", "danbo_raster.h", "danbo_partmap.h", "danbo_metrics.h", "danbo_cull.h")      # the core header, then the satellites
+HEADERS = ("danbo_hip.h", "danbo_raster.h", "danbo_partmap.h", "danbo_metrics.h", "danbo_cull.h", "danbo_batch.h", "danbo_grid_cc.h",
+           "danbo_skel.h", "danbo_depth.h")                                     # the core header, then the satellites
 
 
 def bind_headers(paths):
@@ -272,14 +272,18 @@ def lib():
                 f"{LIB_PATH} not found: build it with `make -C danbo-pytorch_amd/csrc` "
                 "(or __graft_entry__.build()).  There is no CPU / PyTorch fallback.")
         l = ctypes.CDLL(LIB_PATH)
-        for h in _BOUND.values():
-            for name, argtypes in h.signatures.items():
-                fn = getattr(l, name)
-                fn.argtypes = argtypes
-                fn.restype = h.restypes[name]
+        # the version first: a library of an older ABI lacks entries too, and the version says more (`int f(void)` needs no types set)
         if l.danbo_abi_version() != C.DANBO_ABI_VERSION:
             raise RuntimeError(f"{LIB_PATH} has ABI version {l.danbo_abi_version()}, {HEADER_PATH} declares {C.DANBO_ABI_VERSION}: "
                                "the library is stale, rebuild it with `make -C danbo-pytorch_amd/csrc`")
+        for h in _BOUND.values():
+            for name, argtypes in h.signatures.items():
+                fn = getattr(l, name, None)
+                if fn is None:
+                    raise RuntimeError(f"{LIB_PATH} has no {name}, which {h.path} declares: "
+                                       "the library is stale, rebuild it with `make -C danbo-pytorch_amd/csrc`")
+                fn.argtypes = argtypes
+                fn.restype = h.restypes[name]
         _lib = l
     return _lib
 

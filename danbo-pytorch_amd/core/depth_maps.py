@@ -1,33 +1,18 @@
 """Depth and normal maps of the volume renderer on the device (include/danbo_depth.h, csrc/k_depth.hip; the definitions are stated
 once in csrc/depth_math.hpp).  The reference forms depth_map = sum(weights * z_vals) in raw2outputs (core/networks/nerf.py:337) and
 drops it; here the expected depth and a level (median) depth come from the final composite's weights and sorted depths, and the
-normal map from the assembled depth and acc frames of the rendered camera itself.  Nothing here reads a result on the host.
-
-The header lies beside danbo_hip.h but outside _hip.HEADERS (the pinned set), so this module binds it at first use, with _hip's
-parser and rule, as core/utils/skeleton_draw.py binds danbo_skel.h."""
-import os
-
+normal map from the assembled depth and acc frames of the rendered camera itself.  Nothing here reads a result on the host."""
 import numpy as np
 import torch
 
 from . import _hip
 
-_ENTRIES = None
 SPACES = {"camera": 0, "world": 1}
 
 
 def _entries():
-    """the two entry points of libdanbo_hip.so, their types set from include/danbo_depth.h at first use"""
-    global _ENTRIES
-    if _ENTRIES is None:
-        h = _hip.bind_headers([_hip.HEADER_PATH, os.path.join(os.path.dirname(_hip.HEADER_PATH), "danbo_depth.h")])[1]
-        lib, fns = _hip.lib(), {}
-        for name, argtypes in h.signatures.items():
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = argtypes, h.restypes[name]
-            fns[name] = fn
-        _ENTRIES = fns
-    return _ENTRIES
+    """{name: function} of the entries of include/danbo_depth.h on _hip.lib(), which has bound them"""
+    return {name: getattr(_hip.lib(), name) for name in _hip.header("danbo_depth.h").signatures}
 
 
 def _device_f32(t, name, who, shape=None):
@@ -64,9 +49,8 @@ def composite_depth(weights, z_sorted, level=0.5, flat=None):
     alloc = torch.zeros if flat is not None else torch.empty
     out = alloc(2, R, device=weights.device, dtype=torch.float32)
     with torch.cuda.device(weights.device):
-        _hip.check(_entries()["danbo_depth_composite_fwd"](_hip.ptr(weights), _hip.ptr(z_sorted), R, n, float(level), _hip.ptr(lst),
-                                                           _hip.ptr(cnt), _hip.ptr(out[0]), _hip.ptr(out[1]), _hip.stream()),
-                   "danbo_depth_composite_fwd")
+        _hip.call("danbo_depth_composite_fwd", _hip.ptr(weights), _hip.ptr(z_sorted), R, n, float(level), _hip.ptr(lst), _hip.ptr(cnt),
+                  _hip.ptr(out[0]), _hip.ptr(out[1]), _hip.stream())
     return out[0], out[1]
 
 
@@ -124,7 +108,6 @@ def normal_maps(depth, acc, c2ws, focals, centers=None, cast_mask=None, acc_min=
     out = torch.empty(N, H, W, 3, device=depth.device, dtype=torch.float32)
     valid = torch.empty(N, H, W, device=depth.device, dtype=torch.uint8) if return_valid else None
     with torch.cuda.device(depth.device):
-        _hip.check(_entries()["danbo_depth_normals"](_hip.ptr(depth), _hip.ptr(acc), _hip.ptr(cast_mask), _hip.ptr(c2w), _hip.ptr(intr),
-                                                     N, H, W, float(acc_min), float(jump), SPACES[space], float(background),
-                                                     _hip.ptr(out), _hip.ptr(valid), _hip.stream()), "danbo_depth_normals")
+        _hip.call("danbo_depth_normals", _hip.ptr(depth), _hip.ptr(acc), _hip.ptr(cast_mask), _hip.ptr(c2w), _hip.ptr(intr), N, H, W,
+                  float(acc_min), float(jump), SPACES[space], float(background), _hip.ptr(out), _hip.ptr(valid), _hip.stream())
     return (out, valid) if return_valid else out

@@ -1,31 +1,16 @@
 """Connected components of a density grid's inside set on the device, and the filter that drops the components a caller does not
 want -- the floaters of an extracted mesh -- before marching cubes (include/danbo_grid_cc.h, csrc/k_grid_cc.hip; the definitions
-are stated once in csrc/grid_cc_math.hpp).  The grid never leaves the GPU and nothing here reads a result on the host.
-
-The header lies beside danbo_hip.h but outside _hip.HEADERS (the pinned set), so this module binds it at first use, with _hip's
-parser and rule, as core/load_data.py binds danbo_batch.h."""
-import os
-
+are stated once in csrc/grid_cc_math.hpp).  The grid never leaves the GPU and nothing here reads a result on the host."""
 import torch
 
 from . import _hip
 
-_ENTRIES = None
 _NEG_INF = float("-inf")
 
 
 def _entries():
-    """the three entry points of libdanbo_hip.so, their types set from include/danbo_grid_cc.h at first use"""
-    global _ENTRIES
-    if _ENTRIES is None:
-        h = _hip.bind_headers([_hip.HEADER_PATH, os.path.join(os.path.dirname(_hip.HEADER_PATH), "danbo_grid_cc.h")])[1]
-        lib, fns = _hip.lib(), {}
-        for name, argtypes in h.signatures.items():
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = argtypes, h.restypes[name]
-            fns[name] = fn
-        _ENTRIES = fns
-    return _ENTRIES
+    """{name: function} of the entries of include/danbo_grid_cc.h on _hip.lib(), which has bound them"""
+    return {name: getattr(_hip.lib(), name) for name in _hip.header("danbo_grid_cc.h").signatures}
 
 
 def _grid(sigma, iso, floor, who):
@@ -57,16 +42,14 @@ def grid_components(sigma, iso, floor=_NEG_INF):
     All three are contiguous device tensors; five launches on the current stream, no host read, the same bits on every call."""
     grid = _grid(sigma, iso, floor, "grid_components")
     nx, ny, nz = sigma.shape
-    fns = _entries()
-    n_bytes = fns["danbo_grid_cc_workspace_bytes"](nx, ny, nz)
+    n_bytes = _hip.lib().danbo_grid_cc_workspace_bytes(nx, ny, nz)
     if n_bytes == 0:
         raise _hip.HipError(f"grid_components: unsupported grid {nx} x {ny} x {nz} (each dimension 2 .. 1024, fewer than 2^31 points)")
     ws = torch.empty(n_bytes, device=sigma.device, dtype=torch.uint8)
     labels = torch.empty(nx, ny, nz, device=sigma.device, dtype=torch.int32)
     sizes = torch.empty(nx, ny, nz, device=sigma.device, dtype=torch.int32)
     stats = torch.empty(4, device=sigma.device, dtype=torch.int32)
-    _hip.check(fns["danbo_grid_cc_label"](*grid, _hip.ptr(ws), _hip.ptr(labels), _hip.ptr(sizes), _hip.ptr(stats), _hip.stream()),
-               "danbo_grid_cc_label")
+    _hip.call("danbo_grid_cc_label", *grid, _hip.ptr(ws), _hip.ptr(labels), _hip.ptr(sizes), _hip.ptr(stats), _hip.stream())
     return labels, sizes, stats
 
 
@@ -97,7 +80,6 @@ def keep_components(sigma, iso, floor, labels, sizes, stats, keep_largest=False,
     elif out.dtype != torch.float32 or tuple(out.shape) != shape or out.stride(2) != 1:
         raise ValueError(f"keep_components: out must be a float32 tensor of shape {shape} with innermost stride 1")
     kept = torch.empty(2, device=dev, dtype=torch.int32)
-    _hip.check(_entries()["danbo_grid_cc_keep"](*grid, _hip.ptr(labels), _hip.ptr(sizes), _hip.ptr(stats), 1 if keep_largest else 0,
-                                                 min_points, fill, _hip.ptr(out), out.stride(0), out.stride(1), _hip.ptr(kept),
-                                                 _hip.stream()), "danbo_grid_cc_keep")
+    _hip.call("danbo_grid_cc_keep", *grid, _hip.ptr(labels), _hip.ptr(sizes), _hip.ptr(stats), 1 if keep_largest else 0, min_points, fill,
+              _hip.ptr(out), out.stride(0), out.stride(1), _hip.ptr(kept), _hip.stream())
     return out, kept

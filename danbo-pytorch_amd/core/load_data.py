@@ -230,29 +230,18 @@ class PoseImageDataset:
             out = dict(rays_o=new(3), rays_d=new(3), target_s=new(3), fgs=new(1), bgs=new(3), kp3d=new(24, 3), bones=new(24, 3),
                        skts=new(24, 4, 4), cyls=new(5), cam_idxs=new(dtype=torch.int64), kp_idx=new(dtype=torch.int64))
             at = lambda words: _hip.c_void_p(block.data_ptr() + 4 * words)  # noqa: E731
-            _hip.check(_batch_gather()(                      # (both key tuples are in the order of the C parameters)
-                *(_hip.ptr(tab.get(k)) for k in self.TABLE_KEYS), len(self), len(self.bgs), self.H, self.W,
-                at(0), at(G), at(G + R) if noise is not None else None, G, per, int(self.mask_image),
-                *(_hip.ptr(out[k]) for k in self.BATCH_KEYS), _hip.stream()), "danbo_batch_gather")
+            _hip.call("danbo_batch_gather",                  # (both key tuples are in the order of the C parameters)
+                      *(_hip.ptr(tab.get(k)) for k in self.TABLE_KEYS), len(self), len(self.bgs), self.H, self.W,
+                      at(0), at(G), at(G + R) if noise is not None else None, G, per, int(self.mask_image),
+                      *(_hip.ptr(out[k]) for k in self.BATCH_KEYS), _hip.stream())
         out['N_uniques'] = G
         return out
 
 
-_BATCH_GATHER = None
-
-
 def _batch_gather():
-    """danbo_batch_gather of libdanbo_hip.so, its types set from include/danbo_batch.h at first use: the header lies beside
-    danbo_hip.h but outside _hip.HEADERS (the pinned set), so the module that uses it binds it, with _hip's parser and rule"""
-    global _BATCH_GATHER
-    if _BATCH_GATHER is None:
-        import os
-        from . import _hip
-        h = _hip.bind_headers([_hip.HEADER_PATH, os.path.join(os.path.dirname(_hip.HEADER_PATH), "danbo_batch.h")])[1]
-        fn = _hip.lib().danbo_batch_gather
-        fn.argtypes, fn.restype = h.signatures["danbo_batch_gather"], h.restypes["danbo_batch_gather"]
-        _BATCH_GATHER = fn
-    return _BATCH_GATHER
+    """danbo_batch_gather (include/danbo_batch.h) on _hip.lib(), which has bound it"""
+    from . import _hip
+    return _hip.lib().danbo_batch_gather
 
 
 def batch_iterator(dataset, args, rank=0, world=1, on_device=False):

@@ -2,36 +2,21 @@
 core/utils/skeleton_utils.py: skeleton3d_to_2d :478-491, draw_skeletons_3d / draw_skeletons / draw_skeleton2d :1577-1612, which go
 through cv2.line on the host) -- include/danbo_skel.h, csrc/k_skel.hip; the definitions are stated once in csrc/skel_math.hpp.  The
 coverage rule is this project's own and exact (a pixel is covered iff its centre lies within width / 2 of the segment), not
-cv2.line's.  The frames stay where they are; nothing here reads a result on the host.
-
-The header lies beside danbo_hip.h but outside _hip.HEADERS (the pinned set), so this module binds it at first use, with _hip's
-parser and rule, as core/grid_components.py binds danbo_grid_cc.h."""
-import os
-
+cv2.line's.  The frames stay where they are; nothing here reads a result on the host."""
 import numpy as np
 import torch
 
 from .. import _hip
 from .skeleton_utils import SMPLSkeleton, nerf_c2w_to_extrinsic
 
-_ENTRIES = None
 N_JOINTS = len(SMPLSkeleton.joint_names)
 # the reference's colours by the joint's name: (plain, with flip)
 _COLOURS = {"left": ((100, 149, 237), (0, 128, 128)), "right": ((255, 0, 0), (128, 128, 0)), None: ((46, 204, 13), (128, 0, 128))}
 
 
 def _entries():
-    """the two entry points of libdanbo_hip.so, their types set from include/danbo_skel.h at first use"""
-    global _ENTRIES
-    if _ENTRIES is None:
-        h = _hip.bind_headers([_hip.HEADER_PATH, os.path.join(os.path.dirname(_hip.HEADER_PATH), "danbo_skel.h")])[1]
-        lib, fns = _hip.lib(), {}
-        for name, argtypes in h.signatures.items():
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = argtypes, h.restypes[name]
-            fns[name] = fn
-        _ENTRIES = fns
-    return _ENTRIES
+    """{name: function} of the entries of include/danbo_skel.h on _hip.lib(), which has bound them"""
+    return {name: getattr(_hip.lib(), name) for name in _hip.header("danbo_skel.h").signatures}
 
 
 def bone_colours(flip=False, skel_type=SMPLSkeleton):
@@ -91,8 +76,8 @@ def skeleton3d_to_2d(kps, c2ws, H, W, focals, centers=None):
     w2c, focals_d = up(w2c), up(focals)
     ends = torch.empty(N, N_JOINTS, 4, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        _hip.check(_entries()["danbo_skel_project"](_hip.ptr(kps), _hip.ptr(w2c), _hip.ptr(focals_d), focals.shape[1], _hip.ptr(centers),
-                                                    N, int(H), int(W), _hip.ptr(ends), _hip.stream()), "danbo_skel_project")
+        _hip.call("danbo_skel_project", _hip.ptr(kps), _hip.ptr(w2c), _hip.ptr(focals_d), focals.shape[1], _hip.ptr(centers), N, int(H),
+                  int(W), _hip.ptr(ends), _hip.stream())
     return ends
 
 
@@ -109,8 +94,8 @@ def draw_skeletons(imgs, ends, width=3, flip=False, skel_type=SMPLSkeleton):
     colours = torch.tensor(bone_colours(flip, skel_type), device=imgs.device)
     out = torch.empty(N, H, W, 3, dtype=torch.uint8, device=imgs.device)
     with torch.cuda.device(imgs.device):
-        _hip.check(_entries()["danbo_skel_draw"](_hip.ptr(imgs), 1 if imgs.dtype == torch.float32 else 0, _hip.ptr(ends), _hip.ptr(colours),
-                                                 int(width), N, H, W, _hip.ptr(out), _hip.stream()), "danbo_skel_draw")
+        _hip.call("danbo_skel_draw", _hip.ptr(imgs), 1 if imgs.dtype == torch.float32 else 0, _hip.ptr(ends), _hip.ptr(colours), int(width),
+                  N, H, W, _hip.ptr(out), _hip.stream())
     return out
 
 

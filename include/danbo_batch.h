@@ -9,11 +9,8 @@
  * is 0, a hipError_t, or DANBO_EINVAL (-22, danbo_hip.h) for a rejected argument.  The entry is additive in ABI 9
  * (danbo_abi_version() of danbo_hip.h stays 9).  This header declares no struct and no constant.
  *
- * THIS FILE IS READ BY A PROGRAM, like danbo_hip.h and in the same subset of C (stated at the top of danbo_hip.h).  It is not one
- * of the headers core/_hip.py binds on import: core/load_data.py, the module that calls the entry, parses it at first use with
- * _hip.bind_headers (the same parser and the same rule as for every header beside danbo_hip.h: no struct, no name danbo_hip.h
- * declares) and sets the types on the loaded library; tests/test_batch_host.py checks what the parser derived against the host
- * compiler's view of this file.
+ * THIS FILE IS READ BY A PROGRAM, like danbo_hip.h and in the same subset of C (stated at the top of danbo_hip.h):
+ * danbo-pytorch_amd/core/_hip.py parses it on import and binds it as header("danbo_batch.h").
  */
 #ifndef DANBO_BATCH_H
 #define DANBO_BATCH_H

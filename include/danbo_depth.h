@@ -9,9 +9,8 @@
  * is 0, a hipError_t, or DANBO_EINVAL (-22, danbo_hip.h) for a rejected argument.  The entries are additive in ABI 9
  * (danbo_abi_version() of danbo_hip.h stays 9).  This header declares no struct and no constant.
  *
- * THIS FILE IS READ BY A PROGRAM, like danbo_hip.h and in the same subset of C (stated at the top of danbo_hip.h).  It is not one
- * of the headers core/_hip.py binds on import: core/depth_maps.py, the module that calls the entries, parses it at first use with
- * _hip.bind_headers and sets the types on the loaded library; tests/test_depth_host.py checks what the parser derived.
+ * THIS FILE IS READ BY A PROGRAM, like danbo_hip.h and in the same subset of C (stated at the top of danbo_hip.h):
+ * danbo-pytorch_amd/core/_hip.py parses it on import and binds it as header("danbo_depth.h").
  *
  * Both results are functions of the inputs alone: every operation is a separately rounded fp32 one in an order depth_math.hpp
  * fixes, no atomics; two calls give the same bits.

@@ -9,10 +9,8 @@
  * is 0, a hipError_t, or DANBO_EINVAL (-22, danbo_hip.h) for a rejected argument.  The entries are additive in ABI 9
  * (danbo_abi_version() of danbo_hip.h stays 9).  This header declares no struct and no constant.
  *
- * THIS FILE IS READ BY A PROGRAM, like danbo_hip.h and in the same subset of C (stated at the top of danbo_hip.h).  It is not one
- * of the headers core/_hip.py binds on import: core/grid_components.py, the module that calls the entries, parses it at first use
- * with _hip.bind_headers and sets the types on the loaded library; tests/test_grid_cc_host.py checks what the parser derived against
- * the host compiler's view of this file.
+ * THIS FILE IS READ BY A PROGRAM, like danbo_hip.h and in the same subset of C (stated at the top of danbo_hip.h):
+ * danbo-pytorch_amd/core/_hip.py parses it on import and binds it as header("danbo_grid_cc.h").
  *
  * Definitions.  The grid, its strides, the value read and inside-ness are those of danbo_mesh_count: element (i, j, k) at
  * sigma[i * stride_x + j * stride_y + k], v = max(sigma, floor) with a NaN read as -inf, a point is INSIDE iff v >= iso.  A point's

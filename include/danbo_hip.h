@@ -70,7 +70,12 @@ extern "C" {
  * --render_entropy: declared in danbo_partmap.h beside this file, as the rasteriser's entries are in danbo_raster.h);
  * danbo_image_metrics_workspace_bytes, danbo_image_metrics (PSNR / SSIM sums of rendered frames on the device, --eval_device:
  * declared in danbo_metrics.h beside this file); danbo_bone_cull_rays (depths, in-volume words and rows of the listed rays of a
- * frame only, which danbo_render_frame uses beside rays of constants: declared in danbo_cull.h beside this file). */
+ * frame only, which danbo_render_frame uses beside rays of constants: declared in danbo_cull.h beside this file);
+ * danbo_batch_gather (the ray batch of a training step from tables resident on the device: declared in danbo_batch.h);
+ * danbo_grid_cc_workspace_bytes, danbo_grid_cc_label, danbo_grid_cc_keep (connected components of a density grid's inside set and
+ * the filter that drops floaters before extraction: declared in danbo_grid_cc.h); danbo_skel_project, danbo_skel_draw (the
+ * skeleton overlay, --render_skel: declared in danbo_skel.h); danbo_depth_composite_fwd, danbo_depth_normals (depth and normal
+ * maps of the volume renderer, --render_depth: declared in danbo_depth.h). */
 #define DANBO_ABI_VERSION 9   /* what danbo_abi_version() of a library built from this header returns; the binding refuses another */
 int danbo_abi_version(void);
 int danbo_device_info(int* cu_count, int* lds_bytes, char* arch, int arch_len);

@@ -9,10 +9,8 @@
  * is 0, a hipError_t, or DANBO_EINVAL (-22, danbo_hip.h) for a rejected argument.  The entries are additive in ABI 9
  * (danbo_abi_version() of danbo_hip.h stays 9).  This header declares no struct and no constant.
  *
- * THIS FILE IS READ BY A PROGRAM, like danbo_hip.h and in the same subset of C (stated at the top of danbo_hip.h).  It is not one
- * of the headers core/_hip.py binds on import: core/utils/skeleton_draw.py, the module that calls the entries, parses it at first
- * use with _hip.bind_headers and sets the types on the loaded library; tests/test_skel_host.py checks what the parser derived
- * against the host compiler's view of this file.
+ * THIS FILE IS READ BY A PROGRAM, like danbo_hip.h and in the same subset of C (stated at the top of danbo_hip.h):
+ * danbo-pytorch_amd/core/_hip.py parses it on import and binds it as header("danbo_skel.h").
  *
  * Definitions (csrc/skel_math.hpp has them in full).  Frames are [N,H,W,3], N 1 .. 2^20, H and W 1 .. 4096.  ends [N,24,4] int32
  * holds per frame and bone j the segment {ax, ay, bx, by} from joint j to its parent in pixels, x along W; ax = INT32_MIN marks a

@@ -1,6 +1,5 @@
 """Helpers of the training-batch tests (tests/test_batch_host.py, tests/test_gpu_batch.py): the serial restatement of
-csrc/batch_math.hpp (batch_gather_host) built with g++ at test time, the toy data set both files draw from, and the binding of
-include/danbo_batch.h as core/load_data.py makes it."""
+csrc/batch_math.hpp (batch_gather_host) built with g++ at test time, and the toy data set both files draw from."""
 import ctypes
 import os
 
@@ -34,7 +33,6 @@ extern "C" int ref_batch_gather(''' + _PARAMS + ''') {
 }
 '''
 ARGTYPES = [ctypes.c_void_p] * 12 + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 11
-LETTERS = "i:" + "P" * 12 + "iiii" + "PPP" + "iii" + "P" * 11 + "P"          # danbo_batch_gather: the above and the stream
 
 
 def host_lib():
@@ -42,13 +40,6 @@ def host_lib():
     lib = hostlib.build("batch_ref", _WRAPPER % os.path.join(CSRC, "batch_math.hpp"))
     lib.ref_batch_gather.argtypes = ARGTYPES
     return lib
-
-
-def header():
-    """include/danbo_batch.h bound as core/load_data.py binds it -> (namespace of bind_headers, path)"""
-    from core import _hip
-    path = os.path.join(os.path.dirname(_hip.HEADER_PATH), "danbo_batch.h")
-    return _hip.bind_headers([_hip.HEADER_PATH, path])[1], path
 
 
 # ----------------------------------------------------------------------------- the toy data set

@@ -51,8 +51,6 @@ void ref_depth_wave_scan(float* x) { depth_wave_scan(x); }
 _c = ctypes
 COMPOSITE_ARGTYPES = [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_float, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]
 NORMALS_ARGTYPES = [_c.c_void_p] * 5 + [_c.c_int] * 3 + [_c.c_float, _c.c_float, _c.c_int, _c.c_float, _c.c_void_p, _c.c_void_p]
-# "result:parameters" in the letters of tests/test_abi_binding.py, the stream last
-LETTERS = {"danbo_depth_composite_fwd": "i:PPiifPPPPP", "danbo_depth_normals": "i:PPPPPiiiffifPPP"}
 
 
 def host_lib():
@@ -63,13 +61,6 @@ def host_lib():
     lib.ref_depth_wave_scan.argtypes = [_c.c_void_p]
     lib.ref_depth_wave_scan.restype = None
     return lib
-
-
-def header():
-    """include/danbo_depth.h bound as core/depth_maps.py binds it -> (namespace of bind_headers, path)"""
-    from core import _hip
-    path = os.path.join(os.path.dirname(_hip.HEADER_PATH), "danbo_depth.h")
-    return _hip.bind_headers([_hip.HEADER_PATH, path])[1], path
 
 
 def same_bits(a, b):

@@ -1,6 +1,6 @@
 """Helpers of the grid-component tests (tests/test_grid_cc_host.py, tests/test_gpu_grid_cc.py): the serial restatement of
 csrc/grid_cc_math.hpp (grid_cc_host / grid_keep_host) built with g++ at test time, the scipy / numpy predictions it is checked
-against, the test grids, and the binding of include/danbo_grid_cc.h as core/grid_components.py makes it."""
+against, and the test grids."""
 import ctypes
 import functools
 import os
@@ -36,10 +36,6 @@ _c = ctypes
 _GRID = [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_long, _c.c_long, _c.c_float, _c.c_float]
 LABEL_ARGTYPES = _GRID + [_c.c_void_p] * 3
 KEEP_ARGTYPES = _GRID + [_c.c_void_p] * 3 + [_c.c_int, _c.c_int, _c.c_float, _c.c_void_p, _c.c_long, _c.c_long, _c.c_void_p]
-# "result:parameters" in the letters of tests/test_abi_binding.py, the stream last
-LETTERS = {"danbo_grid_cc_workspace_bytes": "z:iii",
-           "danbo_grid_cc_label": "i:PiiillffPPPPP",
-           "danbo_grid_cc_keep": "i:PiiillffPPPiifPllPP"}
 
 
 def host_lib():
@@ -48,13 +44,6 @@ def host_lib():
     lib.ref_grid_cc.argtypes = LABEL_ARGTYPES
     lib.ref_grid_keep.argtypes = KEEP_ARGTYPES
     return lib
-
-
-def header():
-    """include/danbo_grid_cc.h bound as core/grid_components.py binds it -> (namespace of bind_headers, path)"""
-    from core import _hip
-    path = os.path.join(os.path.dirname(_hip.HEADER_PATH), "danbo_grid_cc.h")
-    return _hip.bind_headers([_hip.HEADER_PATH, path])[1], path
 
 
 def grid_args(sigma, iso, floor):

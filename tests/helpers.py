@@ -22,6 +22,11 @@ def hip_lib():
     return _hip.lib()
 
 
+def entry(name):
+    """one entry point of it, its types set from the header that declares it"""
+    return getattr(hip_lib(), name)
+
+
 def T(x, dtype=torch.float32):
     return torch.tensor(np.ascontiguousarray(x), dtype=dtype, device=DEV)
 

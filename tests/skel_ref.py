@@ -1,7 +1,7 @@
 """Helpers of the skeleton-overlay tests (tests/test_skel_host.py, tests/test_gpu_skel.py): an independent restatement of the
 definitions of csrc/skel_math.hpp -- numpy float32 for the projection, Python integers (exact at any size) for the coverage rule and
 the paint order --, the serial restatement of the header itself (skel_project_host / skel_draw_host) built with g++ at test time,
-the named cases, and the binding of include/danbo_skel.h as core/utils/skeleton_draw.py makes it."""
+and the named cases."""
 import ctypes
 import functools
 import os
@@ -49,8 +49,6 @@ int ref_skel_in_box(const int32_t* e, int x, int y, int width) { return skel_in_
 _c = ctypes
 PROJECT_ARGTYPES = [_c.c_void_p] * 3 + [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]
 DRAW_ARGTYPES = [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p] + [_c.c_int] * 4 + [_c.c_void_p]
-# "result:parameters" in the letters of tests/test_abi_binding.py, the stream last
-LETTERS = {"danbo_skel_project": "i:PPPiPiiiPP", "danbo_skel_draw": "i:PiPPiiiiPP"}
 
 
 def host_lib():
@@ -63,13 +61,6 @@ def host_lib():
     lib.ref_skel_quant.argtypes = [_c.c_float]
     lib.ref_skel_covers.argtypes = lib.ref_skel_in_box.argtypes = [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int]
     return lib
-
-
-def header():
-    """include/danbo_skel.h bound as core/utils/skeleton_draw.py binds it -> (namespace of bind_headers, path)"""
-    from core import _hip
-    path = os.path.join(os.path.dirname(_hip.HEADER_PATH), "danbo_skel.h")
-    return _hip.bind_headers([_hip.HEADER_PATH, path])[1], path
 
 
 def same_bits(a, b):

@@ -164,6 +164,15 @@ SATELLITES = {
                             constants={}, history="danbo_image_metrics_workspace_bytes, danbo_image_metrics"),
     "danbo_cull.h": dict(functions={"danbo_bone_cull_rays": "i:PPPPPPPiiiPPPPPPiPPPP"},      # 21 parameters, the stream last
                          constants={}, history="danbo_bone_cull_rays"),
+    "danbo_batch.h": dict(functions={"danbo_batch_gather": "i:PPPPPPPPPPPPiiiiPPPiiiPPPPPPPPPPPP"},      # 12 tables, 4 sizes, the draw
+                          constants={}, history="danbo_batch_gather"),                 # (3 pointers, 3 ints), 11 outputs, the stream
+    "danbo_grid_cc.h": dict(functions={"danbo_grid_cc_workspace_bytes": "z:iii", "danbo_grid_cc_label": "i:PiiillffPPPPP",
+                                       "danbo_grid_cc_keep": "i:PiiillffPPPiifPllPP"},
+                            constants={}, history="danbo_grid_cc_workspace_bytes, danbo_grid_cc_label, danbo_grid_cc_keep"),
+    "danbo_skel.h": dict(functions={"danbo_skel_project": "i:PPPiPiiiPP", "danbo_skel_draw": "i:PiPPiiiiPP"},
+                         constants={}, history="danbo_skel_project, danbo_skel_draw"),
+    "danbo_depth.h": dict(functions={"danbo_depth_composite_fwd": "i:PPiifPPPPP", "danbo_depth_normals": "i:PPPPPiiiffifPPP"},
+                          constants={}, history="danbo_depth_composite_fwd, danbo_depth_normals"),
 }
 
 
@@ -230,6 +239,9 @@ def test_bind_headers_binds_each_header_into_tables_of_its_own(tmp_path):
     assert vars(first.C) == {"DANBO_FIRST": 1} and not first.structs
     assert probe.signatures == {"danbo_probe": [ctypes.c_float, ctypes.c_void_p]} and probe.restypes == {"danbo_probe": ctypes.c_int}
     assert vars(probe.C) == {} and probe.path == str(tmp_path / "danbo_probe.h")
+    # a tenth header beside the real nine, through the call that binds the table: no clash, and only its own names
+    tenth = _hip.bind_headers([_hip.header(name).path for name in _hip.HEADERS] + [probe.path])[-1]
+    assert tenth.signatures == probe.signatures and tenth.restypes == probe.restypes and vars(tenth.C) == {}
 
 
 @pytest.mark.parametrize("text, error, quoted", [
@@ -330,5 +342,16 @@ def test_a_library_of_another_abi_version_is_refused(monkeypatch):
     monkeypatch.setattr(_hip, "_lib", None)
     monkeypatch.setattr(_hip.C, "DANBO_ABI_VERSION", 10)
     with pytest.raises(RuntimeError, match="ABI version 9.*declares 10.*stale"):
+        _hip.lib()
+    assert _hip._lib is None
+
+
+def test_a_library_that_lacks_a_declared_entry_is_refused(monkeypatch):
+    """a library built before a header of the table gained an entry has the same ABI version: lib() names what is missing"""
+    h = _hip.header("danbo_depth.h")
+    monkeypatch.setattr(_hip, "_lib", None)
+    monkeypatch.setitem(h.signatures, "danbo_not_there", [ctypes.c_float, ctypes.c_void_p])
+    monkeypatch.setitem(h.restypes, "danbo_not_there", ctypes.c_int)
+    with pytest.raises(RuntimeError, match=r"has no danbo_not_there, which \S*danbo_depth\.h declares.*stale, rebuild it with `make -C"):
         _hip.lib()
     assert _hip._lib is None

@@ -90,16 +90,16 @@ def guards_intact(bufs):
 
 
 def call_entry(ds, per, picks, pixels, noise, shift=0):
-    from core import _hip, load_data
+    from core import _hip
     t = {k: (None if v is None else torch.tensor(v, device=DEV)) for k, v in ref.tables_of(ds).items()}
     R = len(picks) * per
     bufs, views = guarded_outputs(R, shift)
     d_picks, d_pixels = torch.tensor(picks, device=DEV), torch.tensor(pixels, device=DEV)
     d_noise = None if noise is None else torch.tensor(noise, device=DEV)
     assert d_picks.dtype == d_pixels.dtype == torch.int32
-    rc = load_data._batch_gather()(*(_hip.ptr(t[k]) for k in ref.TABLES), len(ds), len(ds.bgs), ds.H, ds.W, _hip.ptr(d_picks),
-                                   _hip.ptr(d_pixels), _hip.ptr(d_noise), len(picks), per, int(ds.mask_image),
-                                   *(_hip.ptr(views[k]) for k in ref.KEYS), _hip.stream())
+    rc = hip_lib().danbo_batch_gather(*(_hip.ptr(t[k]) for k in ref.TABLES), len(ds), len(ds.bgs), ds.H, ds.W, _hip.ptr(d_picks),
+                                      _hip.ptr(d_pixels), _hip.ptr(d_noise), len(picks), per, int(ds.mask_image),
+                                      *(_hip.ptr(views[k]) for k in ref.KEYS), _hip.stream())
     torch.cuda.synchronize()
     assert rc == 0, rc
     return bufs, {k: v.cpu().numpy() for k, v in views.items()}

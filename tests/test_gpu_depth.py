@@ -10,18 +10,13 @@ import pytest
 import torch
 
 import depth_ref as ref
-from helpers import DEV, EINVAL, ROOT, T, same_bits
+from helpers import DEV, EINVAL, ROOT, entry, T, same_bits
 from test_gpu_part_maps import MAPS, S_E2E, SF_E2E, cast, clone, danbo_caster, danbo_engine      # the part-map tests' synthetic builders
 
 pytestmark = pytest.mark.gpu
 F32, F64, U = ref.F32, ref.F64, ref.U
 N_GUARD = 64          # guard words on either side of an output
 N_E2E = S_E2E + SF_E2E        # 12 + 6: the samples of the part-map end-to-end frames
-
-
-def entries():
-    from core import depth_maps
-    return depth_maps._entries()
 
 
 def stream_ptr():
@@ -51,8 +46,8 @@ def gpu_composite(w, z, level, ray_list=None, ray_count=None):
     (buf_d, d), (buf_l, l) = guarded(R, torch.float32, fill), guarded(R, torch.float32, fill)
     lst = None if ray_list is None else dev(np.asarray(ray_list, np.int32))
     cnt = None if ray_count is None else dev(np.array([ray_count], np.int32))
-    rc = entries()["danbo_depth_composite_fwd"](w.data_ptr(), z.data_ptr(), R, n, float(level), None if lst is None else lst.data_ptr(),
-                                                None if cnt is None else cnt.data_ptr(), d.data_ptr(), l.data_ptr(), stream_ptr())
+    rc = entry("danbo_depth_composite_fwd")(w.data_ptr(), z.data_ptr(), R, n, float(level), None if lst is None else lst.data_ptr(),
+                                            None if cnt is None else cnt.data_ptr(), d.data_ptr(), l.data_ptr(), stream_ptr())
     assert rc == 0, rc
     torch.cuda.synchronize()
     assert intact(buf_d, fill) and intact(buf_l, fill), "a guard word was overwritten"
@@ -64,9 +59,9 @@ def gpu_normals(c, jump, space, with_cast=True, acc_min=0.5, background=1.0):
     depth, acc, cast, c2w, intr = (dev(c[k]) for k in ("depth", "acc", "cast", "c2w", "intr"))
     N, H, W = depth.shape
     (buf_r, rgb), (buf_v, valid) = guarded(N * H * W * 3, torch.float32, -5.0), guarded(N * H * W, torch.uint8, 0xA5)
-    rc = entries()["danbo_depth_normals"](depth.data_ptr(), acc.data_ptr(), cast.data_ptr() if with_cast else None, c2w.data_ptr(),
-                                          intr.data_ptr(), N, H, W, acc_min, jump, space, background, rgb.data_ptr(), valid.data_ptr(),
-                                          stream_ptr())
+    rc = entry("danbo_depth_normals")(depth.data_ptr(), acc.data_ptr(), cast.data_ptr() if with_cast else None, c2w.data_ptr(),
+                                      intr.data_ptr(), N, H, W, acc_min, jump, space, background, rgb.data_ptr(), valid.data_ptr(),
+                                      stream_ptr())
     assert rc == 0, rc
     torch.cuda.synchronize()
     assert intact(buf_r, -5.0) and intact(buf_v, 0xA5), "a guard word was overwritten"
@@ -148,7 +143,7 @@ def test_rejected_arguments_leave_the_outputs_untouched():
     spare = torch.zeros(8, dtype=torch.int32, device=DEV)
     ptrs = dict(weights=w.data_ptr(), z_sorted=z.data_ptr(), depth=d.data_ptr(), depth_level=l.data_ptr(), ray_list=spare.data_ptr(),
                 ray_count=spare.data_ptr())
-    call = entries()["danbo_depth_composite_fwd"]
+    call = entry("danbo_depth_composite_fwd")
     assert call(*ref.composite_args(ptrs), stream_ptr()) == 0
     torch.cuda.synchronize()
     assert same_bits(d.cpu().numpy(), ref.composite_expected(18, 0.5)[0][:4])
@@ -163,7 +158,7 @@ def test_rejected_arguments_leave_the_outputs_untouched():
     depth, acc = depth.contiguous(), acc.contiguous()
     rgb = torch.full((4 * 4 * 3,), 77.0, device=DEV)
     ptrs = dict(depth=depth.data_ptr(), acc=acc.data_ptr(), c2w=c2w.data_ptr(), intr=intr.data_ptr(), out_rgb=rgb.data_ptr())
-    call = entries()["danbo_depth_normals"]
+    call = entry("danbo_depth_normals")
     for kw in ref.NORMALS_REJECTS:
         assert call(*ref.normals_args(ptrs, **kw), stream_ptr()) == EINVAL, kw
     torch.cuda.synchronize()

@@ -11,17 +11,12 @@ import torch
 
 import grid_cc_ref as ref
 import mesh_ref as m
-from helpers import DEV, EINVAL, ROOT, golden, T, same_bits
+from helpers import DEV, EINVAL, ROOT, entry, golden, T, same_bits
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
 INF = float("inf")
 GUARD32 = int(np.array(m.GUARD, np.uint32).view(np.int32))
-
-
-def entries():
-    from core import grid_components
-    return grid_components._entries()
 
 
 def stream_ptr():
@@ -57,14 +52,14 @@ def gpu_label(t, iso, floor, want_sizes=True):
     """the raw C call with guard words around labels, sizes, stats and a workspace of exactly danbo_grid_cc_workspace_bytes
     -> labels, sizes (or None), stats as device tensors"""
     n = t.numel()
-    n_bytes = entries()["danbo_grid_cc_workspace_bytes"](*t.shape)
+    n_bytes = entry("danbo_grid_cc_workspace_bytes")(*t.shape)
     assert n_bytes > 0 and n_bytes % 4 == 0
     w_buf, ws = guarded_t(n_bytes // 4)
     l_buf, labels = guarded_t(n)
     s_buf, sizes = guarded_t(n)
     t_buf, stats = guarded_t(4)
-    rc = entries()["danbo_grid_cc_label"](*grid_of(t, iso, floor), ws.data_ptr(), labels.data_ptr(), sizes.data_ptr() if want_sizes else None,
-                                          stats.data_ptr(), stream_ptr())
+    rc = entry("danbo_grid_cc_label")(*grid_of(t, iso, floor), ws.data_ptr(), labels.data_ptr(), sizes.data_ptr() if want_sizes else None,
+                                      stats.data_ptr(), stream_ptr())
     assert rc == 0, rc
     torch.cuda.synchronize()
     assert intact(w_buf, l_buf, s_buf, t_buf), "a guard word was overwritten"
@@ -86,8 +81,8 @@ def gpu_keep(t, iso, floor, labels, sizes, stats, keep_largest, min_points, fill
         src = o
     assert (o.stride() == t.stride()) == (out != "other")
     k_buf, kept = guarded_t(2)
-    rc = entries()["danbo_grid_cc_keep"](*grid_of(src, iso, floor), labels.data_ptr(), sizes.data_ptr(), stats.data_ptr(), int(keep_largest),
-                                         int(min_points), float(fill), o.data_ptr(), o.stride(0), o.stride(1), kept.data_ptr(), stream_ptr())
+    rc = entry("danbo_grid_cc_keep")(*grid_of(src, iso, floor), labels.data_ptr(), sizes.data_ptr(), stats.data_ptr(), int(keep_largest),
+                                     int(min_points), float(fill), o.data_ptr(), o.stride(0), o.stride(1), kept.data_ptr(), stream_ptr())
     assert rc == 0, rc
     torch.cuda.synchronize()
     assert intact(o_buf, k_buf), "a guard word was overwritten"
@@ -143,7 +138,7 @@ def test_rejected_arguments_leave_the_outputs_untouched():
     n = t.numel()
     labels, sizes, stats = gpu_label(t, iso, floor)
     bufs = {k: torch.full((n_words,), GUARD32, dtype=torch.int32, device=DEV)
-            for k, n_words in dict(ws=entries()["danbo_grid_cc_workspace_bytes"](*t.shape) // 4, labels=n, sizes=n, stats=4, out=n, kept=2).items()}
+            for k, n_words in dict(ws=entry("danbo_grid_cc_workspace_bytes")(*t.shape) // 4, labels=n, sizes=n, stats=4, out=n, kept=2).items()}
     p = {k: b.data_ptr() for k, b in bufs.items()}
     nx, ny, nz = t.shape
     sx, sy = t.stride(0), t.stride(1)
@@ -153,14 +148,14 @@ def test_rejected_arguments_leave_the_outputs_untouched():
                  stats=p["stats"])
         assert set(kw) <= set(a)
         a.update(kw)
-        return entries()["danbo_grid_cc_label"](*a.values(), stream_ptr())
+        return entry("danbo_grid_cc_label")(*a.values(), stream_ptr())
 
     def keep(**kw):
         a = dict(sigma=t.data_ptr(), nx=nx, ny=ny, nz=nz, sx=sx, sy=sy, floor=floor, iso=iso, labels=labels.data_ptr(), sizes=sizes.data_ptr(),
                  stats=stats.data_ptr(), keep_largest=1, min_points=0, fill=-1., out=p["out"], osx=sx, osy=sy, kept=p["kept"])
         assert set(kw) <= set(a)
         a.update(kw)
-        return entries()["danbo_grid_cc_keep"](*a.values(), stream_ptr())
+        return entry("danbo_grid_cc_keep")(*a.values(), stream_ptr())
 
     grid_cases = [dict(sigma=None), dict(sigma=t.data_ptr() + 2), dict(nx=1), dict(nz=1025), dict(ny=0), dict(sx=-sx), dict(sy=-1),
                   dict(iso=INF), dict(iso=float("nan")), dict(floor=INF), dict(floor=float("nan"))]

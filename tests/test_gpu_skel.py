@@ -9,17 +9,12 @@ import pytest
 import torch
 
 import skel_ref as ref
-from helpers import DEV, EINVAL, ROOT, same_bits
+from helpers import DEV, EINVAL, ROOT, entry, same_bits
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
 J = ref.J
 N_GUARD = 64          # guard bytes / words on either side of an output
-
-
-def entries():
-    from core.utils import skeleton_draw
-    return skeleton_draw._entries()
 
 
 def stream_ptr():
@@ -47,8 +42,8 @@ def gpu_project(c):
     centers = None if c["centers"] is None else dev(c["centers"])
     N = len(c["kps"])
     buf, ends = guarded(N * J * 4, torch.int32, 0x5AFEC0D)
-    rc = entries()["danbo_skel_project"](kps.data_ptr(), w2c.data_ptr(), focals.data_ptr(), c["focals"].shape[1],
-                                         None if centers is None else centers.data_ptr(), N, c["H"], c["W"], ends.data_ptr(), stream_ptr())
+    rc = entry("danbo_skel_project")(kps.data_ptr(), w2c.data_ptr(), focals.data_ptr(), c["focals"].shape[1],
+                                     None if centers is None else centers.data_ptr(), N, c["H"], c["W"], ends.data_ptr(), stream_ptr())
     assert rc == 0, rc
     torch.cuda.synchronize()
     assert intact(buf, 0x5AFEC0D), "a guard word was overwritten"
@@ -60,8 +55,8 @@ def gpu_draw(src, ends, table, w):
     N, H, W, _ = src.shape
     buf, dst = guarded(N * H * W * 3, torch.uint8, 0xA5)
     colours = dev(table)
-    rc = entries()["danbo_skel_draw"](src.data_ptr(), int(src.dtype == torch.float32), ends.data_ptr(), colours.data_ptr(), w, N, H, W,
-                                      dst.data_ptr(), stream_ptr())
+    rc = entry("danbo_skel_draw")(src.data_ptr(), int(src.dtype == torch.float32), ends.data_ptr(), colours.data_ptr(), w, N, H, W,
+                                  dst.data_ptr(), stream_ptr())
     assert rc == 0, rc
     torch.cuda.synchronize()
     assert intact(buf, 0xA5), "a guard byte was overwritten"
@@ -106,8 +101,8 @@ def test_sources_and_outputs_at_odd_addresses(name):
             src.copy_(dev(host))
             buf = torch.full((n + 2 * N_GUARD,), 0xA5, dtype=torch.uint8, device=DEV)
             dst = buf[N_GUARD + shift:N_GUARD + shift + n]
-            rc = entries()["danbo_skel_draw"](src.data_ptr(), int(is_float), ends.data_ptr(), table.data_ptr(), 3, *host.shape[:3],
-                                              dst.data_ptr(), stream_ptr())
+            rc = entry("danbo_skel_draw")(src.data_ptr(), int(is_float), ends.data_ptr(), table.data_ptr(), 3, *host.shape[:3],
+                                          dst.data_ptr(), stream_ptr())
             assert rc == 0, rc
             torch.cuda.synchronize()
             assert bool((buf[:N_GUARD + shift] == 0xA5).all()) and bool((buf[N_GUARD + shift + n:] == 0xA5).all())
@@ -125,13 +120,13 @@ def test_rejected_arguments_leave_the_outputs_untouched():
         a = dict(src=src.data_ptr(), src_is_float=1, ends=ends.data_ptr(), colours=table.data_ptr(), width=3, N=1, H=64, W=64, dst=out.data_ptr())
         assert set(kw) <= set(a)
         a.update(kw)
-        return entries()["danbo_skel_draw"](*a.values(), stream_ptr())
+        return entry("danbo_skel_draw")(*a.values(), stream_ptr())
 
     def project(**kw):
         a = dict(kps=kps.data_ptr(), w2c=w2c.data_ptr(), focals=focals.data_ptr(), focal_stride=1, centers=None, N=1, H=64, W=64, ends=e_out.data_ptr())
         assert set(kw) <= set(a)
         a.update(kw)
-        return entries()["danbo_skel_project"](*a.values(), stream_ptr())
+        return entry("danbo_skel_project")(*a.values(), stream_ptr())
 
     for kw in [dict(src=None), dict(ends=None), dict(colours=None), dict(dst=None), dict(width=0), dict(width=65), dict(H=0), dict(W=4097),
                dict(N=0), dict(src_is_float=2), dict(dst=src.data_ptr()), dict(dst=src.data_ptr() + 64), dict(src=src.data_ptr() + 2),

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import skel_ref as ref
-from helpers import ADDR as P, EINVAL        # P: an address no check follows
+from helpers import ADDR as P, EINVAL, ROOT, entry        # P: an address no check follows
 
 F32 = np.float32
 J, SKIP, LIMIT = ref.J, ref.SKIP, ref.LIMIT
@@ -224,32 +224,14 @@ def test_quantisation_is_numpys_made_total():
 
 
 # ----------------------------------------------------------------------------- the header and its binding
-def test_header_is_a_satellite_outside_the_pinned_set(tmp_path_factory):
+def test_header_is_a_satellite_of_the_table():
+    """what tests/test_abi_binding.py's referee does not hold: the host restatement is typed as the header types the entries"""
     from core import _hip
-    from core.utils import skeleton_draw
-    from test_abi_binding import INCLUDE, bound_letters, compiled_signatures, declared_functions, same_class
-    assert "danbo_skel.h" not in _hip.HEADERS
-    h, path = ref.header()
-    assert os.path.samefile(path, os.path.join(INCLUDE, "danbo_skel.h"))
-    with open(path) as f:
-        text = f.read()
-    functions, structs, constants = _hip.parse_header(text)
-    names = list(ref.LETTERS)
-    assert sorted(declared_functions(text)) == sorted(names) == sorted(functions) == sorted(h.signatures) and not structs and not constants
-    for other in _hip.HEADERS:
-        o = _hip.header(other)
-        assert not set(h.signatures) & set(o.signatures) and not set(vars(h.C)) & set(vars(o.C))
-    seen = compiled_signatures(tmp_path_factory, ["danbo_skel.h", "danbo_hip.h", "danbo_skel.h"], names)
-    assert seen == ref.LETTERS
-    raw = ctypes.CDLL(_hip.lib()._name)
-    fns = skeleton_draw._entries()
-    for name in names:
-        assert same_class(seen[name]) == bound_letters(h, name) == ref.LETTERS[name]
-        assert hasattr(raw, name), name                              # every declared entry is exported by the built library
-        assert fns[name].argtypes == h.signatures[name] and fns[name].restype is h.restypes[name]
+    assert "danbo_skel.h" in _hip.HEADERS
+    h = _hip.header("danbo_skel.h")
+    assert os.path.samefile(h.path, os.path.join(ROOT, "include", "danbo_skel.h"))
     assert h.signatures["danbo_skel_project"] == ref.PROJECT_ARGTYPES + [ctypes.c_void_p]          # + the stream
     assert h.signatures["danbo_skel_draw"] == ref.DRAW_ARGTYPES + [ctypes.c_void_p]
-    assert _hip.lib().danbo_abi_version() == _hip.C.DANBO_ABI_VERSION == 9
 
 
 # ----------------------------------------------------------------------------- argument checks (no GPU: nothing is launched)
@@ -266,20 +248,18 @@ _ids = lambda kw: "-".join(f"{k}={_show(v)}" for k, v in kw.items())      # noqa
 
 
 def project_call(**kw):
-    from core.utils import skeleton_draw
     a = dict(kps=P, w2c=P, focals=P, focal_stride=1, centers=None, N=1, H=4, W=4, ends=P)
     assert set(kw) <= set(a)
     a.update(kw)
-    return skeleton_draw._entries()["danbo_skel_project"](*(a[k] for k in _PROJECT), None)
+    return entry("danbo_skel_project")(*(a[k] for k in _PROJECT), None)
 
 
 def draw_call(**kw):
-    from core.utils import skeleton_draw
     # (dst far from src: the ranges of a 4 x 4 frame do not meet)
     a = dict(src=P, src_is_float=1, ends=P, colours=P, width=3, N=1, H=4, W=4, dst=P + 4096)
     assert set(kw) <= set(a)
     a.update(kw)
-    return skeleton_draw._entries()["danbo_skel_draw"](*(a[k] for k in _DRAW), None)
+    return entry("danbo_skel_draw")(*(a[k] for k in _DRAW), None)
 
 
 _DIMS = [dict(H=0), dict(H=4097), dict(W=0), dict(W=4097), dict(N=0), dict(N=-1), dict(H=-4)]

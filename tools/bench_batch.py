@@ -75,7 +75,7 @@ def kernel_time(ds, steps, warmup):
     """danbo_batch_gather alone on one fixed draw: device events around `steps` back-to-back launches -> seconds per launch"""
     import numpy as np
     import torch
-    from core import _hip, load_data
+    from core import _hip
     import batch_ref as ref
     per, picks, pixels, noise = ref.draw(ds, N_IMAGES, N_RAND)
     tab = ds._device["tables"]
@@ -83,7 +83,7 @@ def kernel_time(ds, steps, warmup):
     d = [torch.tensor(x, device=DEV) for x in (picks, pixels)] + [None if noise is None else torch.tensor(noise, device=DEV)]
     out = {k: torch.empty((R,) + ref.ROWS[k], dtype=torch.int64 if k in ("cam_idxs", "kp_idx") else torch.float32, device=DEV)
            for k in ref.KEYS}
-    fn = load_data._batch_gather()
+    fn = _hip.lib().danbo_batch_gather
     args = [*(_hip.ptr(tab.get(k)) for k in ref.TABLES), len(ds), len(ds.bgs), ds.H, ds.W, *(_hip.ptr(x) for x in d), len(picks), per,
             int(ds.mask_image), *(_hip.ptr(out[k]) for k in ref.KEYS), _hip.stream()]
     times = []

@@ -70,7 +70,7 @@ def rate(n_bytes, ms, copy_tbs):
 def main():
     import bench
     import depth_ref as ref
-    from core import depth_maps, hip_ops as ops
+    from core import _hip, hip_ops as ops
     probe = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "probe", "hbm_rate.py")], capture_output=True, text=True,
                            timeout=300, check=True).stdout
     print(probe.strip())
@@ -90,16 +90,16 @@ def main():
           f"rays with acc >= 0.5: {int((keep['acc_map'] >= 0.5).sum())}")
 
     # ---- the two launches alone
-    fns = depth_maps._entries()
+    lib = _hip.lib()
     P = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())      # noqa: E731
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     out = torch.zeros(2, R, device=DEV)
 
     def composite_all():
-        assert fns["danbo_depth_composite_fwd"](P(w), P(z), R, n, 0.5, None, None, P(out[0]), P(out[1]), st) == 0
+        assert lib.danbo_depth_composite_fwd(P(w), P(z), R, n, 0.5, None, None, P(out[0]), P(out[1]), st) == 0
 
     def composite_listed():
-        assert fns["danbo_depth_composite_fwd"](P(w), P(z), R, n, 0.5, P(flat["ray_list"]), P(flat["ray_count"]), P(out[0]), P(out[1]), st) == 0
+        assert lib.danbo_depth_composite_fwd(P(w), P(z), R, n, 0.5, P(flat["ray_list"]), P(flat["ray_count"]), P(out[0]), P(out[1]), st) == 0
     ms_all, ms_listed = timed([composite_all, composite_listed])
     composite_all()
     torch.cuda.synchronize()
@@ -120,7 +120,7 @@ def main():
     valid = torch.empty(1, H, W, dtype=torch.uint8, device=DEV)
 
     def normals():
-        assert fns["danbo_depth_normals"](P(depth), P(acc), P(cast), P(c2w), P(intr), 1, H, W, 0.5, 0.0, 0, 1.0, P(rgb), P(valid), st) == 0
+        assert lib.danbo_depth_normals(P(depth), P(acc), P(cast), P(c2w), P(intr), 1, H, W, 0.5, 0.0, 0, 1.0, P(rgb), P(valid), st) == 0
     ms_n, = timed([normals])
     torch.cuda.synchronize()
     want = ref.host_normals(depth.cpu().numpy(), acc.cpu().numpy(), cast.cpu().numpy(), c2w.cpu().numpy(), intr.cpu().numpy())

@@ -52,25 +52,24 @@ def host_path(sigma, iso, floor):
 
 def measure(name, sigma, iso, floor, read_tbs):
     from core import _hip
-    from core.grid_components import _entries
     import grid_cc_ref as ref
-    lib, fns = _hip.lib(), _entries()
+    lib = _hip.lib()
     nx, ny, nz = sigma.shape
     n = nx * ny * nz
     P = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     grid = (P(sigma), nx, ny, nz, sigma.stride(0), sigma.stride(1), floor, iso)
-    ws = torch.empty(fns["danbo_grid_cc_workspace_bytes"](nx, ny, nz), dtype=torch.uint8, device=DEV)
+    ws = torch.empty(lib.danbo_grid_cc_workspace_bytes(nx, ny, nz), dtype=torch.uint8, device=DEV)
     labels, sizes = (torch.empty(n, dtype=torch.int32, device=DEV) for _ in range(2))
     stats, kept = torch.empty(4, dtype=torch.int32, device=DEV), torch.empty(2, dtype=torch.int32, device=DEV)
     out = torch.empty_strided(sigma.shape, sigma.stride(), dtype=torch.float32, device=DEV)
     fill = floor if floor < iso else float("-inf")
 
     def label():
-        assert fns["danbo_grid_cc_label"](*grid, P(ws), P(labels), P(sizes), P(stats), st) == 0
+        assert lib.danbo_grid_cc_label(*grid, P(ws), P(labels), P(sizes), P(stats), st) == 0
 
     def keep():
-        assert fns["danbo_grid_cc_keep"](*grid, P(labels), P(sizes), P(stats), 1, 0, fill, P(out), out.stride(0), out.stride(1), P(kept), st) == 0
+        assert lib.danbo_grid_cc_keep(*grid, P(labels), P(sizes), P(stats), 1, 0, fill, P(out), out.stride(0), out.stride(1), P(kept), st) == 0
     ms_l, reps_l = timed_ms(label)
     ms_k, reps_k = timed_ms(keep)
     floor_ms = 12 * n / (read_tbs * 1e9)

@@ -29,8 +29,9 @@ N_FRAMES = 16
 
 def measure(size, copy_tbs):
     import skel_ref as ref
-    from core.utils.skeleton_draw import _entries, bone_colours, skeleton3d_to_2d
-    fns = _entries()
+    from core import _hip
+    from core.utils.skeleton_draw import bone_colours, skeleton3d_to_2d
+    lib = _hip.lib()
     P = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     s = ref.scene(N_FRAMES, size, size, 7, focal_stride=2, with_centers=True)
@@ -38,7 +39,7 @@ def measure(size, copy_tbs):
     ends = torch.empty(N_FRAMES, 24, 4, dtype=torch.int32, device=DEV)
 
     def project():
-        assert fns["danbo_skel_project"](P(kps), P(w2c), P(focals), 2, P(centers), N_FRAMES, size, size, P(ends), st) == 0
+        assert lib.danbo_skel_project(P(kps), P(w2c), P(focals), 2, P(centers), N_FRAMES, size, size, P(ends), st) == 0
     ms_p, reps_p = timed_ms(project)
     same_ends = ref.same_bits(ends.cpu().numpy(), ref.host_project(s["kps"], ref.w2c_of(s["c2ws"]), s["focals"], s["centers"], size, size))
     assert ref.same_bits(skeleton3d_to_2d(kps, s["c2ws"], size, size, s["focals"], s["centers"]).cpu().numpy(), ends.cpu().numpy())
@@ -53,7 +54,7 @@ def measure(size, copy_tbs):
     for kind, src in frames.items():
         for width in (3, 8):
             def draw():
-                assert fns["danbo_skel_draw"](P(src), int(kind == "float32"), P(ends), P(colours), width, N_FRAMES, size, size, P(out), st) == 0
+                assert lib.danbo_skel_draw(P(src), int(kind == "float32"), P(ends), P(colours), width, N_FRAMES, size, size, P(out), st) == 0
             ms, reps = timed_ms(draw)
             n_bytes = pixels * ((12 if kind == "float32" else 3) + 3)
             t0 = time.perf_counter()
