@@ -57,6 +57,12 @@ def config_parser():
     p.add_argument('--mesh_render', nargs='?', const='normal', default=None, choices=['normal', 'color', 'flat'],
                    help='with --render_mesh: the turntable of every mesh (render_mesh.py) straight from the device tensors')
     p.add_argument('--mesh_render_res', nargs=2, type=int, default=[512, 512], help='(H, W) of the turntable frames')
+    p.add_argument('--mesh_score', type=str, default=None, metavar='DIR', help='with --render_mesh: score every extracted mesh NNN '
+                   'against DIR/NNN.ply while it is on the device (core/mesh_score.py).  mesh_scores.npy holds one row per mesh: '
+                   'chamfer_l1, chamfer_l2, normal_consistency, n_points, then precision, recall, fscore of every threshold in the '
+                   'order given; mesh_score_final.txt the column means')
+    p.add_argument('--mesh_score_points', type=int, default=100_000, help='surface samples per mesh of --mesh_score')
+    p.add_argument('--mesh_score_tau', nargs='+', type=float, default=[0.01, 0.02], help='distance thresholds of --mesh_score')
     p.add_argument('--render_confd', action='store_true', help='image.npy holds the part map: every sample coloured by the bone '
                    'with the largest assignment logit')
     p.add_argument('--render_entropy', action='store_true', help='image.npy holds the entropy of the bone assignment, blue (one '
@@ -292,7 +298,8 @@ def evaluate_metric(rgbs, accs, bboxes, gt_dict, basedir, on_device=False):
 
 @torch.no_grad()
 def render_mesh(basedir, render_kwargs, tensor_data, chunk=4096, radius=1.80, res=255, threshold=10., normals=False, colors=False,
-                turntable=None, turntable_res=(512, 512), keep_largest=False, min_points=0):
+                turntable=None, turntable_res=(512, 512), keep_largest=False, min_points=0, score_dir=None, score_points=100_000,
+                score_tau=(0.01, 0.02)):
     """Density on a (res+1)^3 grid around every pose and its isosurface at `threshold` (reference :1266-1281: PyMCubes and trimesh
     there, the library's own extraction kernels and core/utils/mesh_io.py here): `meshes/NNN.ply`, vertices in [-0.5, 0.5]^3, and
     the clamped grid as `meshes/NNN_sigma.npy`.  normals / colors (--mesh_normals / --mesh_colors) add per-vertex unit normals --
@@ -304,7 +311,10 @@ def render_mesh(basedir, render_kwargs, tensor_data, chunk=4096, radius=1.80, re
     keep_largest / min_points (--mesh_keep_largest / --mesh_min_points): the grid's connected components above the threshold are
     labelled on the device and the floaters set to 0 before the extraction (RayCaster.render_mesh_surface); the .ply, the
     turntable and `NNN_sigma.npy` are the filtered grid's, and one line per mesh reports what was found and kept -- the one host
-    read of the filter, after the .ply is written."""
+    read of the filter, after the .ply is written.
+    score_dir (--mesh_score): every mesh is scored against score_dir/NNN.ply from the device tensors (the prediction sampled with
+    seed 0, the file with seed 1, so a mesh against itself shows the sampling floor, not 0): one line per mesh, `mesh_scores.npy`
+    and `mesh_score_final.txt` (core.mesh_score.save_scores).  A missing file is an error before anything is extracted."""
     caster = render_kwargs['ray_caster']
     os.makedirs(os.path.join(basedir, 'meshes'), exist_ok=True)
     want_n, want_c = normals or turntable == 'normal', colors or turntable == 'color'
@@ -313,6 +323,12 @@ def render_mesh(basedir, render_kwargs, tensor_data, chunk=4096, radius=1.80, re
     kps, skts, bones, cams = tensor_data['kp'], tensor_data['skts'], tensor_data['bones'], tensor_data.get('cams')
     filter_kw = dict(keep_largest=bool(keep_largest), min_component=int(min_points), return_components=True) \
         if keep_largest or min_points else {}
+    score_rows, score_tau = [], tuple(float(t) for t in score_tau)
+    if score_dir is not None:
+        from core import mesh_score
+        for i in range(len(kps)):
+            if not os.path.isfile(os.path.join(score_dir, f'{i:03d}.ply')):
+                raise FileNotFoundError(f"--mesh_score: {os.path.join(score_dir, f'{i:03d}.ply')} not found")
     for i in range(len(kps)):
         cam = None if cams is None else cams[i % cams.shape[0]:i % cams.shape[0] + 1]
         verts, faces, *attrs, raw = caster(kps=kps[i:i + 1], skts=skts[i:i + 1], bones=bones[i:i + 1], radius=radius,
@@ -332,6 +348,15 @@ def render_mesh(basedir, render_kwargs, tensor_data, chunk=4096, radius=1.80, re
             frames = render_turntable(verts, faces, normals=attrs[0] if want_n else None, colors=attrs[-1] if want_c else None,
                                       size=turntable_res, shade=turntable)
             np.save(os.path.join(basedir, 'mesh_render', f'{i:03d}.npy'), frames.cpu().numpy())
+        if score_dir is not None:
+            if not (len(verts) and len(faces)):
+                raise ValueError(f'--mesh_score: mesh {i:03d} is empty at threshold {threshold}')
+            s = mesh_score.score_meshes((verts, faces), os.path.join(score_dir, f'{i:03d}.ply'), n_points=score_points,
+                                        thresholds=score_tau, seed=(0, 1))
+            score_rows.append(mesh_score.score_row(s, score_points, score_tau))
+            print(mesh_score.score_line(f'{i:03d}', s, score_tau))
+    if score_dir is not None:
+        mesh_score.save_scores(basedir, score_rows, score_tau)
 
 
 def save_depth_maps(args, basedir, geo, accs, render_data, device):
@@ -366,7 +391,8 @@ def run_render(argv=None):
     if args.render_mesh:
         render_mesh(basedir, render_kwargs, tensor_data, res=args.mesh_res, radius=args.mesh_radius, threshold=args.mesh_threshold,
                     normals=args.mesh_normals, colors=args.mesh_colors, turntable=args.mesh_render,
-                    turntable_res=tuple(args.mesh_render_res), keep_largest=args.mesh_keep_largest, min_points=args.mesh_min_points)
+                    turntable_res=tuple(args.mesh_render_res), keep_largest=args.mesh_keep_largest, min_points=args.mesh_min_points,
+                    score_dir=args.mesh_score, score_points=args.mesh_score_points, score_tau=args.mesh_score_tau)
         return None
     render_kwargs = dict(render_kwargs, render_confd=args.render_confd, render_entropy=args.render_entropy,
                          part_valid_only=args.part_valid_only)
