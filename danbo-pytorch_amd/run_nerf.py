@@ -31,21 +31,23 @@ from core.utils.ray_utils import kp_to_valid_rays  # noqa: E402
 
 def render_path(render_poses, hwf, chunk, render_kwargs, centers=None, kp=None, skts=None, cyls=None, bones=None, gt_imgs=None,
                 bg_imgs=None, bg_indices=None, cams=None, subject_idxs=None, render_factor=0, white_bkgd=False, ret_acc=False,
-                ext_scale=0.00035, base_bg=1.0, device_out=False, ret_depth=False):
+                ext_scale=0.00035, base_bg=1.0, device_out=False, ret_depth=False, frame_rays=None):
     """One image per camera in `render_poses`: only the pixels inside the 2-D box of the pose's bounding cylinder are cast,
     the rest of the image is the background (`bg_imgs[bg_indices[i]]` resized, white, or black).  Pose tensors with fewer
     entries than cameras are cycled (`i % n`).  -> rgbs [N,H,W,3], disps [N,H,W,1], accs, valid_idxs, bboxes: numpy arrays, one
     device-to-host copy per frame; with device_out the stacked DEVICE tensors (nan_to_num applied there), nothing copied.
     ret_depth: the rays are cast with render_depth=True (depth_level from render_kwargs, default 0.5) and a sixth element follows:
     dict(depth=[N,H,W] the expected depth sum w z, depth_med=[N,H,W] the level depth, cast=[N,H,W] bool: the pixel was cast),
-    assembled like the acc frames -- 0 outside the cast box -- and on the device or the host as the other frames are."""
+    assembled like the acc frames -- 0 outside the cast box -- and on the device or the host as the other frames are.
+    frame_rays: the result of core.motion.frame_rays for these cameras and poses (rays and indices already on the device) in place
+    of kp_to_valid_rays, which is then not called."""
     H, W, focal = hwf
     if render_factor != 0:
         H, W = H // render_factor, W // render_factor
         focal = focal / render_factor
         centers = centers / render_factor if centers is not None else None
-    rays, valid_idxs, cyls, bboxes = kp_to_valid_rays(render_poses, H, W, focal, kps=kp, cylinder_params=cyls, skts=skts,
-                                                      ext_scale=ext_scale, centers=centers)
+    rays, valid_idxs, cyls, bboxes = frame_rays if frame_rays is not None else kp_to_valid_rays(
+        render_poses, H, W, focal, kps=kp, cylinder_params=cyls, skts=skts, ext_scale=ext_scale, centers=centers)
     dev = kp.device
 
     def per_image(x, i, n_rays):

@@ -7,9 +7,11 @@
 A trained model (the reference's `args.txt` + `.tar` checkpoint formats) is rendered along a generated camera / pose
 sequence -- `bullet` (camera ring around selected poses), `interpolate` (axis-angle blend between selected poses), `bubble`
 (camera wobbling around its position), `val` /
-`selected` (the data's own cameras) -- or sampled on a density grid (`--render_mesh`).  The sequence generators take arrays
-instead of the reference's HDF5 paths (no h5py / deepdish here); `--dataset synthetic` builds them from seeded poses, `--dataset
-npz --entry file.npz` reads them.  Outputs: `image/`, `acc/` as .npy stacks (no imageio here), `bboxes.npy`, with
+`selected` (the data's own cameras), `retarget` (runs of the data's frames, or with `--motion FILE` a motion of one's own driven
+through the trained skeleton), `animate` (listed joints blended between selected poses; for these two the chain, the cylinders and
+the rays of every frame are made on the device, core/motion.py, unless `--motion_chain host`) -- or sampled on a density grid
+(`--render_mesh`).  The sequence generators take arrays instead of the reference's HDF5 paths (no h5py / deepdish here);
+`--dataset synthetic` builds them from seeded poses, `--dataset npz --entry file.npz` reads them.  Outputs: `image/`, `acc/` as .npy stacks (no imageio here), `bboxes.npy`, with
 `--eval` `scores.npy` + `score_final.txt` like the reference, and with `--render_skel` the reference's `skel/` as `skel.npy`:
 every frame with its posed skeleton drawn over it on the device (core/utils/skeleton_draw.py).  `--render_depth` adds `depth.npy`
 (the expected depth sum w z of every pixel of the rendered camera, float32 [N,H,W], 0 outside the cast box) and `depth_med.npy`
@@ -25,6 +27,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from core.config import config_parser as nerf_config_parser, txt_to_argstring  # noqa: E402
+from core import motion  # noqa: E402
 from core.depth_maps import normal_maps  # noqa: E402
 from core.load_data import PoseImageDataset, generate_bullet_time, get_dataset  # noqa: E402
 from core.raycasters import create_raycaster  # noqa: E402
@@ -44,7 +47,8 @@ def config_parser():
     p.add_argument('--dataset', type=str, required=True, help="'synthetic' or 'npz'")
     p.add_argument('--entry', type=str, required=True, help='catalog entry: a split name (synthetic) or an .npz path')
     p.add_argument('--white_bkgd', action='store_true')
-    p.add_argument('--render_type', type=str, default='bullet', help='bullet | interpolate | bubble | pose_rotate | selected | val')
+    p.add_argument('--render_type', type=str, default='bullet', help='bullet | interpolate | bubble | pose_rotate | selected | val | '
+                   'retarget | animate')
     p.add_argument('--render_mesh', action='store_true', help='sample the density grid instead of rendering images')
     p.add_argument('--mesh_res', type=int, default=255)
     p.add_argument('--mesh_radius', type=float, default=1.8)
@@ -84,6 +88,25 @@ def config_parser():
     p.add_argument('--normal_acc_min', type=float, default=0.5, help='with --render_normal: a pixel below this opacity has no normal')
     p.add_argument('--normal_jump', type=float, default=0., help='with --render_normal: > 0 leaves out neighbours whose depth differs '
                    'by more (no normals across depth edges)')
+    p.add_argument('--retarget_len', type=int, default=1, help='retarget: frames of the run that starts at every selected index')
+    p.add_argument('--retarget_skip', type=int, default=1, help='retarget: every k-th frame of a run')
+    p.add_argument('--motion', type=str, default=None, metavar='FILE', help='retarget: drive the model with the poses of an .npz '
+                   '(bones [F,24,3] axis-angles or rotmats [F,24,3,3]; optional root [F,3] or kp3d [F,24,3]) instead of the data\'s own')
+    p.add_argument('--motion_start', type=int, default=0, help='with --motion: the first frame of the file')
+    p.add_argument('--motion_len', type=int, default=None, help='with --motion: frames of the file from --motion_start (default: all)')
+    p.add_argument('--motion_skip', type=int, default=1, help='with --motion: every k-th of them')
+    p.add_argument('--motion_cam', type=int, default=0, help='with --motion: the data frame whose camera sees the motion and at whose '
+                   'root its first frame stands')
+    p.add_argument('--motion_travel', action='store_true', help='with --motion: add the file\'s root displacement relative to its '
+                   'first frame')
+    p.add_argument('--animate_joints', nargs='+', type=int, default=None, help='animate: the joints that are blended between the '
+                   'selected poses (0 .. 23)')
+    p.add_argument('--from_rest', action='store_true', help='animate: the first pose\'s joints other than the root start at zero')
+    p.add_argument('--center_kps', action='store_true', help='retarget / animate: every pose\'s root at the origin')
+    p.add_argument('--undo_rot', action='store_true', help='retarget / animate: the reference\'s fixed root rotation')
+    p.add_argument('--motion_chain', type=str, default='device', choices=['device', 'host'], help='retarget / animate: where the '
+                   'kinematic chain, the bounding cylinders and the rays of every frame are made: on the device (core/motion.py) or '
+                   'by the host path of the other render types')
     p.add_argument('--selected_idxs', nargs='+', type=int, default=None)
     p.add_argument('--selected_framecode', type=int, default=None)
     p.add_argument('--n_bullet', type=int, default=10)
@@ -242,8 +265,26 @@ def get_render_dataset(args, nerf_args, device):
     return get_dataset(nerf_args, device=device)
 
 
-def load_render_data(args, nerf_args, dataset):
-    """-> (render_data for `render_path`, gt_dict for evaluation)"""
+MOTION_TYPES = ('retarget', 'animate')
+
+
+def load_motion_sequence(args, dataset, focals, centers, sel):
+    """the sequence (core.motion: bones, roots, cameras) of --render_type retarget / animate"""
+    if args.render_type == 'animate':
+        if args.animate_joints is None:
+            raise ValueError("--render_type animate needs --animate_joints")
+        return motion.load_animate(dataset.kp3d, dataset.bones, dataset.c2ws, focals, dataset.rest_pose, sel, args.animate_joints,
+                                   n_step=args.n_step, from_rest=args.from_rest, undo_rot=args.undo_rot, center_kps=args.center_kps)
+    if args.motion is not None:
+        return motion.load_motion(args.motion, dataset.kp3d, dataset.c2ws, focals, cam=args.motion_cam, start=args.motion_start,
+                                  length=args.motion_len, skip=args.motion_skip, travel=args.motion_travel, centers=centers)
+    return motion.load_retarget(dataset.kp3d, dataset.bones, dataset.c2ws, focals, dataset.rest_pose, sel, length=args.retarget_len,
+                                skip=args.retarget_skip, centers=centers, center_kps=args.center_kps, undo_rot=args.undo_rot)
+
+
+def load_render_data(args, nerf_args, dataset, device=None):
+    """-> (render_data for `render_path`, gt_dict for evaluation).  retarget / animate with --motion_chain device: kp, skts and cyls
+    are tensors on `device` (default: the current one), made there from the sequence's bones and roots by core.motion.pose_chain."""
     H0, W0 = dataset.H, dataset.W
     H, W = args.render_res if args.render_res is not None else (H0, W0)
     scale = float(H) / float(H0)
@@ -267,12 +308,25 @@ def load_render_data(args, nerf_args, dataset):
         kps, skts, c2ws, cam_idxs, focals, bones, centers = load_selected(*src, centers=centers)
         if scale == 1.0:
             gt.update(gt_paths=dataset.imgs[sel], gt_mask_paths=dataset.fgs[sel], bg_imgs=dataset.bgs, bg_indices=dataset.bg_idxs[sel])
+    elif args.render_type in MOTION_TYPES:
+        seq = load_motion_sequence(args, dataset, focals, centers, sel)
+        c2ws, cam_idxs, focals, bones, centers = seq['c2ws'], seq['cam_idxs'], seq['focals'], seq['bones'], seq['centers']
+        if args.motion_chain == 'host':
+            kps, skts = _pose_chain(bones, dataset.rest_pose, seq['roots'][:, None])
+        else:
+            dev = device if device is not None else torch.device('cuda', torch.cuda.current_device() if torch.cuda.is_available() else 0)
+            up = lambda x: torch.tensor(np.ascontiguousarray(x), dtype=torch.float32, device=dev)      # noqa: E731
+            pose = dict(rots=up(seq['rotmats'])) if seq['rotmats'] is not None else dict(bones=up(bones))
+            chain = motion.pose_chain(**pose, rest_pose=up(dataset.rest_pose), roots=up(seq['roots']), ext_scale=nerf_args.ext_scale)
+            kps, skts, cyls = chain['kps'], chain['skts'], chain['cyls']
     else:
         raise NotImplementedError(f"render_type '{args.render_type}'")
     if args.selected_framecode is not None:
         cam_idxs = np.full_like(cam_idxs, args.selected_framecode)
     data = dict(render_poses=c2ws, hwf=(int(H), int(W), focals.astype(np.float32)), centers=centers, kp=kps, skts=skts,
                 bones=bones, cams=cam_idxs if nerf_args.opt_framecode else None)
+    if args.render_type in MOTION_TYPES and args.motion_chain == 'device':
+        data['cyls'] = cyls
     return data, gt
 
 
@@ -384,7 +438,7 @@ def run_render(argv=None):
     nerf_args, unknown = nerf_config_parser().parse_known_args(txt_to_argstring(args.nerf_args))
     print(f'UNKNOWN ARGS: {unknown}')
     render_kwargs, dataset = load_nerf(args, nerf_args, device)
-    render_data, gt_dict = load_render_data(args, nerf_args, dataset)
+    render_data, gt_dict = load_render_data(args, nerf_args, dataset, device)
     tensor_data = to_tensors(render_data, device)
     basedir = os.path.join(args.outputdir, args.runname)
     os.makedirs(basedir, exist_ok=True)
@@ -399,9 +453,14 @@ def run_render(argv=None):
     want_depth = args.render_depth or args.render_normal
     if want_depth:
         render_kwargs['depth_level'] = args.depth_level
+    frame_rays = None
+    if args.render_type in MOTION_TYPES and args.motion_chain == 'device':
+        # the boxes from one read of the cylinders, the rays of every frame made where they are cast
+        frame_rays = motion.frame_rays(render_data['render_poses'], *render_data['hwf'], tensor_data['kp'], tensor_data['cyls'],
+                                       centers=render_data['centers'])
     rgbs, _, accs, _, bboxes, *geo = render_path(render_kwargs=render_kwargs, chunk=nerf_args.chunk, ext_scale=nerf_args.ext_scale,
                                                  ret_acc=True, white_bkgd=args.white_bkgd, device_out=args.eval_device,
-                                                 ret_depth=want_depth, **tensor_data)
+                                                 ret_depth=want_depth, frame_rays=frame_rays, **tensor_data)
     if want_depth and not args.no_save:
         save_depth_maps(args, basedir, geo[0], accs, render_data, device)
     scores = None
